@@ -1,7 +1,15 @@
 """Benchmark: LoMPC QP solves/sec on MI355X (BASELINE.json metric, config 3/4).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--mode path|direct]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--mode path|direct] [--dump-outputs DIR] [--full]
     torchrun --nproc-per-node N bench.py --gpus N ...   (one rank per GPU, RCCL)
+
+A plain run does only what the headline figure needs: set up, warm up, time the K steps, write the
+last timed step's outputs (``--dump-outputs DIR``: w, cost, set_sum_w, set_stats as DIR/<name>.npy,
+fp64, at most 64 MB — the same arrays from run to run with the same arguments) and print the line
+(``roofline.traffic`` is read from the committed profiles/pmc.json when it matches the configuration:
+a file read, no run).
+``--full`` adds every other leg described below (the bitwise re-run of the timed steps, ``kernels``,
+``contracts``, ``cpu_baseline``, ``direct_mode``, ``bimpc``, ``collective``), each after the timed region.
 
 One step = one batched price iteration of a whole charging-station time step on
 this rank's EV shard: for each EV type (small, large) load P = 12 fresh
@@ -62,6 +70,16 @@ def parse():
     ap.add_argument("--partitions", type=int, default=12)
     ap.add_argument("--mode", choices=["path", "direct"], default="path")
     ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run every other leg: the bitwise re-run of the timed steps, the "
+                         "per-kernel breakdown, the contract legs, the CPU baselines, DIRECT mode, the BiMPC station "
+                         "and (sharded) the collective's cost; the --no-* options below drop single legs of it")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (w, cost, set_sum_w, set_stats) as DIR/<name>.npy "
+                         "(fp64, at most 64 MB in all: beyond that a fixed seeded sample of the per-EV rows, whose row "
+                         "indices are rows.npy, stored as fp64 like the rest — cast to int to index); several plans "
+                         "(--mode direct, --split-types): names prefixed small_ / large_; several ranks: rank 0 "
+                         "writes its own shard's w and cost and the combined set reductions, the others nothing")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cells", type=int, default=4,
                     help="gamma cells per parameter set of the benchmark's plan (0: the plan's default, 16 at these "
@@ -128,6 +146,54 @@ def check_env():
     bad = sorted(k for k in os.environ if k.startswith("LOMPC_"))
     if bad:
         raise SystemExit(f"bench.py: diagnostic variables set ({', '.join(bad)}); unset them for a measured run")
+
+
+DUMP_BYTES = 64 * 10 ** 6  # --dump-outputs writes at most this much in all
+
+
+def dump_rows(n_rows: int, row_bytes: int, budget: int, seed: int):
+    """The per-EV rows --dump-outputs keeps of ``n_rows`` rows of ``row_bytes`` each: None (all of
+    them) while they fit ``budget`` bytes, otherwise a sorted sample without replacement that depends
+    only on (seed, n_rows, the count that fits) — the same rows in every run with the same arguments.
+    A sampled dump also stores its row indices (8 B per row, counted here)."""
+    if n_rows * row_bytes <= budget:
+        return None
+    keep = max(budget // (row_bytes + 8), 1)
+    return np.sort(np.random.default_rng([int(seed), n_rows, 0xD0]).choice(n_rows, size=keep, replace=False))
+
+
+def dump_outputs(dirname, runs, names, outs_t, seed, torch):
+    """--dump-outputs: what the timed path computed in its last step, as ``dirname``/<name>.npy (fp64):
+    per plan its ``w`` (B, N) and ``cost`` (B,) buffers — every timed step rewrites them, the last one's
+    remain — and the last step's set reductions ``set_sum_w`` (S, N) / ``set_stats`` (S, 8) (the last
+    slice of the timed call's per-step records, else the plan's own buffers).  One plan: those names;
+    several (--mode direct, --split-types): prefixed with the EV type.  Beyond DUMP_BYTES in all the
+    per-EV rows are a fixed seeded sample (dump_rows), its indices in ``rows.npy`` (as fp64)."""
+    os.makedirs(dirname, exist_ok=True)
+    torch.cuda.synchronize()
+    sets, rows = [], []
+    for r, name in zip(runs, names):
+        pre = f"{name}_" if len(runs) > 1 else ""
+        out = r["plan"].out
+        for k in ("set_sum_w", "set_stats"):
+            t = outs_t[k][-1] if outs_t is not None and k in outs_t else out.get(k)
+            if t is not None:
+                sets.append((pre + k, t))
+        per_ev = [(pre + k, out[k]) for k in ("w", "cost") if out.get(k) is not None]
+        if per_ev:
+            rows.append((pre, per_ev))
+    budget = DUMP_BYTES - sum(8 * t.numel() for _, t in sets) - 4096  # (the files' headers)
+    for k, t in sets:
+        np.save(os.path.join(dirname, k + ".npy"), t.cpu().numpy().astype(np.float64, copy=False))
+    for pre, per_ev in rows:
+        n = int(per_ev[0][1].shape[0])
+        idx = dump_rows(n, sum(8 * int(np.prod(t.shape[1:])) for _, t in per_ev), budget // len(rows), seed)
+        if idx is not None:
+            np.save(os.path.join(dirname, pre + "rows.npy"), idx.astype(np.float64))
+            sel = torch.as_tensor(idx, device=per_ev[0][1].device)
+        for k, t in per_ev:
+            a = (t if idx is None else t.index_select(0, sel)).cpu().numpy()
+            np.save(os.path.join(dirname, k + ".npy"), a.astype(np.float64, copy=False))
 
 
 def main():
@@ -268,7 +334,7 @@ def main():
         K = args.steps
         outs_t = {k: torch.empty((K,) + tuple(pl.out[k].shape), dtype=torch.float64, device=dev)
                   for k in ("set_sum_w", "set_stats") if pl.out.get(k) is not None}
-        outs_v = {k: torch.empty_like(v) for k, v in outs_t.items()}
+        outs_v = {k: torch.empty_like(v) for k, v in outs_t.items()} if args.full else None  # (verify_steps)
     # warmup (and correctness gate: every QP certified) — in the timed region's own form, so its
     # one-time setup (the stepped form's tables and block map) is not timed; the warmup carries the
     # timed call's HIP events too (the runtime's first timed dispatch on a queue costs host time), and
@@ -322,6 +388,9 @@ def main():
         rep, fail, inv = r["plan"].check()  # sticky device tallies: EVERY timed step's QPs
         assert fail == 0 and inv == 0, (fail, inv)
         repaired += rep
+    if args.dump_outputs and rank == 0:  # (before any later leg runs the plan again)
+        dump_outputs(args.dump_outputs, runs, [e["name"] for e in eng], outs_t if batched else None, args.seed, torch)
+    full = args.full
     # the per-EV kernel's timing over the timed region: HIP events on its own dispatches
     k_ms, k_n, k_qps = 0.0, 0, 0
     for r in runs:
@@ -329,9 +398,9 @@ def main():
         k_ms += ms
         k_n += n
         k_qps += r["qps"] * n
-    verified = verify_steps(runs[0], args, outs_t, outs_v, torch) if batched else None
+    verified = verify_steps(runs[0], args, outs_t, outs_v, torch) if batched and full else None
     gpu_last = None  # the last timed step's GPU outputs (host copies), for the CPU engine's parity check
-    if batched and args.mode == "path" and not args.no_cpu_baseline and runs[0]["plan"].out.get("w") is not None:
+    if full and batched and args.mode == "path" and not args.no_cpu_baseline and runs[0]["plan"].out.get("w") is not None:
         pl = runs[0]["plan"]
         gpu_last = {"w": pl.out["w"].cpu().numpy(), "cost": pl.out["cost"].cpu().numpy(),
                     "set_sum_w": outs_t["set_sum_w"][-1].cpu().numpy(), "set_stats": outs_t["set_stats"][-1].cpu().numpy()}
@@ -417,16 +486,17 @@ def main():
         "repaired_qps": repaired,
         "host_issue_us_per_step": t_issue / args.steps * 1e6,
         "verified_steps": verified["steps"] if verified else 0,
-        "verification": verified or "per-step issue: no per-step records kept",
+        "verification": verified or ("per-step issue: no per-step records kept" if full or not batched else
+                                     "not run (--full re-runs every timed step and compares bit for bit)"),
     }
-    if sharded:
+    if sharded and full:
         line["collective"] = collective_cost(runs, args, world, dev, torch, dist, comm, batched, dt)
     pmc = load_pmc(args, N, qp_per_launch)
     pk = kname if stepped else "k_eval"
     if pmc and pk in pmc and "hbm_bytes_per_launch" in pmc[pk]:
         line["roofline"]["traffic"] = pmc[pk]["hbm_bytes_per_launch"]
         line["roofline"]["traffic_source"] = pmc["source"]
-    if path and world == 1 and len(runs) == 1:
+    if full and path and world == 1 and len(runs) == 1:
         line["kernels"] = kernel_breakdown(runs[0], step, args, nsteps, pmc, torch)
         if stepped:
             line["kernels"][kname] = {"avg_us": avg_launch_s * 1e6, "launches_timed": k_n,
@@ -436,17 +506,17 @@ def main():
                                                "three different steps); the entries above: each kernel as its own launch")}
             if pmc and kname in pmc:
                 line["kernels"][kname]["pmc"] = {x: pmc[kname][x] for x in pmc[kname] if x != "hbm_bytes_per_launch"}
-    if path and world == 1 and not multi and not args.no_contracts:
+    if full and path and world == 1 and not multi and not args.no_contracts:
         line["contracts"] = contract_legs(eng, runs[0], N, P, args, nsteps, dev, torch, comm, pmc)
         if batched and comm is None:
             line["contracts"]["sequential"] = sequential_leg(runs[0], eng, N, P, args, torch)
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         line["cpu_baseline"] = cpu_baseline(eng, N, args.cpu_seconds, args.seed)
         if path:
             line["cpu_baseline"]["same_algorithm"] = cpu_same_algorithm(eng, N, P, args, gpu_last)
-    if path and world == 1 and not args.no_direct:
+    if full and path and world == 1 and not args.no_direct:
         line["direct_mode"] = direct_leg(eng, N, P, args, nsteps, dev, torch)
-    if not args.no_station:
+    if full and not args.no_station:
         del eng, runs
         line["bimpc"] = station_leg(args, world, dev, sharded)
     if rank == 0:
@@ -757,6 +827,8 @@ def contract_legs(eng, run, N, P, args, nsteps, dev, torch, comm, pmc):
     out["reductions"] = sorted_reductions_leg(base, lm_ptr, lr_ptr, stride, args, torch, comm, red)
     # the headline's workload with every step's rows in their OWN buffer (w at a per-step stride: K x 50 MB
     # of fresh lines, which the 256 MB Infinity Cache cannot hold — the HBM-resident form of the roofline)
+    # (as many of the K steps as a quarter of the free device memory holds: all of them up to a thousand steps)
+    K = max(1, min(K, torch.cuda.mem_get_info(dev)[0] // 4 // (8 * base.B * (N + 1))))
     base.profile(enable=("k_eval",))
     o = {"w": torch.empty((K, base.B, N), dtype=torch.float64, device=dev),
          "cost": torch.empty((K, base.B), dtype=torch.float64, device=dev)}

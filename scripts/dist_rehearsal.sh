@@ -5,6 +5,6 @@ cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}" || exit 1
 export TMPDIR=/tmp
 mkdir -p gpurun_out
 timeout -k 10 400 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 \
-  --master-port 29511 bench.py --gpus 2 --steps 5 --warmup 2 --dist-backend gloo --station-evs-per-gpu 65536 \
+  --master-port 29511 bench.py --full --gpus 2 --steps 5 --warmup 2 --dist-backend gloo --station-evs-per-gpu 65536 \
   > gpurun_out/dist2.log 2>&1
 rc=$?; echo "dist2 rc=$rc"; exit $rc

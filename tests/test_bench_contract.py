@@ -35,6 +35,42 @@ def test_bench_refuses_diagnostic_env():
     assert r.returncode != 0 and "LOMPC_HOST_LOOP" in (r.stderr + r.stdout)
 
 
+def test_bench_full_and_dump_options():
+    """``--full`` is off by default (a plain run times the steps and nothing else) and the --no-*
+    options still parse beside it; ``--dump-outputs`` takes the directory."""
+    import bench
+
+    argv = sys.argv
+    try:
+        sys.argv = ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "2"]
+        a = bench.parse()
+        assert (a.full, a.dump_outputs, a.steps, a.warmup) == (False, None, 7, 2)
+        sys.argv = ["bench.py", "--full", "--no-station", "--dump-outputs", "some/dir"]
+        a = bench.parse()
+        assert a.full and a.no_station and a.dump_outputs == "some/dir"
+    finally:
+        sys.argv = argv
+
+
+def test_dump_rows_budget_and_determinism():
+    """--dump-outputs keeps every per-EV row while they fit the byte budget; beyond it a sorted sample
+    without replacement that fits (indices included) and is the same for the same arguments."""
+    import bench
+
+    row = 8 * 25  # (w row of N = 24 and the cost)
+    assert bench.dump_rows(262144, row, bench.DUMP_BYTES, 0) is None  # the default workload: whole
+    assert bench.dump_rows(0, row, bench.DUMP_BYTES, 0) is None
+    n, budget = 100000, 10 ** 6
+    assert bench.dump_rows(budget // row, row, budget, 0) is None  # exactly full
+    idx = bench.dump_rows(n, row, budget, 3)
+    assert idx.dtype.kind == "i" and len(idx) == budget // (row + 8) and len(idx) * (row + 8) <= budget
+    assert np.all(np.diff(idx) > 0) and idx[0] >= 0 and idx[-1] < n
+    assert np.array_equal(idx, bench.dump_rows(n, row, budget, 3))
+    assert not np.array_equal(idx, bench.dump_rows(n, row, budget, 4))
+    big = bench.dump_rows(2 ** 22, row, bench.DUMP_BYTES, 0)  # (stored as fp64: exact)
+    assert np.array_equal(big, big.astype(np.float64).astype(np.int64))
+
+
 def test_combine_rows_rank_order():
     from lompc_amd import _lib
     from lompc_amd.dist import combine_rows

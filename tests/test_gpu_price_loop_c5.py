@@ -6,8 +6,8 @@ three consecutive partitions of 87 381 EVs (= 2^20 / 12), charge levels uniform 
 station's partition ranges (np.linspace(MIN_INITIAL_SOC, y_max, P + 1), charging_station.py:
 85-90), laid out as the station lays them out (descending charge level, each partition's plan
 staged ahead, stage_partition / use_partition), run through ``PriceSolver.compute_optimal_prices``
-in its default form — the device-resident loop, one ``k_loop_iter`` launch per price iteration —
-with prev_prices chaining the partitions (price_solver.py:104, :166).  The checker is the CPU
+in its default form — the device-resident loop, the whole loop in one persistent ``k_loop_run2``
+launch — with prev_prices chaining the partitions (price_solver.py:104, :166).  The checker is the CPU
 oracle loop (oracle/price_oracle.py: the C oracle's dense active set per EV, warm-started along the
 sorted batch, a dense scipy NNLS price QP, the documented LP vertex rule).  w_ref = 0.8 w_max U[0,1]^N
 takes the loop through 5-30 iterations per partition (measured with the oracle).
@@ -44,7 +44,7 @@ def test_device_price_loop_matches_oracle_at_config5_partitions(gpu, monkeypatch
     c, lc = consts(ev)
     rng = np.random.default_rng(500 + (ev == "large"))
     ps = PriceSolver(N, lc, "linear-convex", device=0)
-    assert ps.device_loop and ps.native_loop  # the default: k_loop_iter, one launch per iteration
+    assert ps.device_loop and ps.native_loop  # the default: k_loop_run2, one persistent launch per loop
     po = PO.OraclePriceSolver(N, c, "linear-convex")
     po.warm = True
     edges = np.linspace(MIN_INITIAL_SOC, c.y_max, 13)
@@ -60,7 +60,16 @@ def test_device_price_loop_matches_oracle_at_config5_partitions(gpu, monkeypatch
         ps.use_partition(p)
         po.set_charge_levels(y0)
         n0 = ps.n_batched_calls
+        plan = ps._plan
+        plan.profile(enable=("k_path", "k_eval"))
+        for k in ("k_path", "k_eval"):
+            plan.profile(read=True, reset=True, kernel=k)
         lm, st = ps.compute_optimal_prices(w_ref, 0.0)
+        launches = {k: plan.profile(read=True, kernel=k)[1] for k in ("k_path", "k_eval")}
+        plan.profile(enable=False)
+        # the persistent kernel ran (not the host loop lompc_price_loop can fall back to): one launch
+        # timed as k_path for the whole loop, no evaluation launch, the default 6 cells per set
+        assert launches == {"k_path": 1, "k_eval": 0} and plan.info()["cells"] == ps.loop_cells == 6, (p, launches)
         lmo, sto = po.compute_optimal_prices(w_ref, 0.0)
         assert st["iter"] == sto["iter"], (p, st["iter"], sto["iter"])
         assert ps.n_batched_calls - n0 == st["iter"] + 1
@@ -76,7 +85,7 @@ def test_device_price_loop_matches_oracle_at_config5_partitions(gpu, monkeypatch
         np.testing.assert_allclose(w0, w0o, rtol=0, atol=1e-6)
         assert abs(p0 - p0o) <= 1e-6 * max(1.0, abs(p0o)), (p, p0, p0o)
         iters.append(st["iter"])
-    assert sum(iters) >= 10, iters  # tens of iterations through k_loop_iter, not a trivial loop
+    assert sum(iters) >= 10, iters  # tens of iterations through k_loop_run2, not a trivial loop
 
 
 @pytest.mark.parametrize("ev", ["small", "large"])

@@ -10,7 +10,7 @@ the station at seed 0, expected outputs from the CPU oracle loop, oracle/price_o
 Each is followed by the next partition of its type's chain (4 096 of its EVs), whose loop starts from
 the long loop's final prices (prev_prices, price_solver.py:104, :166; charging_station.py:275-307).
 Both partitions run through ``PriceSolver.compute_optimal_prices_chain`` — the station's default path:
-the device loop (one ``k_loop_iter`` launch per price iteration) then ``lompc_price_regularize``,
+the device loop (the whole loop in one persistent ``k_loop_run2`` launch) then ``lompc_price_regularize``,
 the next partition from those prices, in one native call.
 
 Tolerance (what is asserted):

@@ -831,6 +831,12 @@ bool polish(const Bimpc& B, std::vector<double>& z, std::vector<double>& llo, st
     Jn.push_back(J[a]);
     lgn[J[a]] = std::max(nu[a], 0.0);
   }
+  if (changed) {
+    // a row was released: without its multiplier the residuals below are not this solve's (a free
+    // variable's would miss the bar and end the polish) — solve again on the smaller set first
+    J = Jn;
+    continue;
+  }
   mulEt(N, lgn.data(), tN.data());
   mulLt(B, tN.data(), tn.data());
   llon.assign(n, 0.0);

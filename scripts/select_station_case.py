@@ -1,0 +1,111 @@
+"""CPU selection of the mid-size cases of tests/test_gpu_station.py::test_closed_loop_matches_oracle:
+for each (n_lo, n_bi) the smallest M_2 (from 512) and the first seed whose ORACLE trajectory
+(oracle/station_oracle.py, no GPU) meets all of
+
+* several pieces per loop: in at least half of the populated (type, partition, step) price loops the
+  oracle's per-EV optima at the loop's final prices show >= 2 distinct active-set patterns (each stage
+  at 0, at w_max, or interior);
+* the state moves: at least one EV of each type that was not re-drawn changes partition, and
+  ncharged_s + ncharged_l > 0 (a re-draw happened);
+* no count on a knife-edge: every average error the loops test (the deciding one included) is at least
+  1e-6 tol away from tol, so niter is unchanged under a 1e-6 relative perturbation;
+* the oracle is cheap: the trajectory's seconds are printed (ps.warm = "state" and get_w0_price0_batch:
+  the same optima; the dense BiMPC interior point takes about 2.5 s per step whatever M_2).
+
+Prints one line per candidate and stops at the first that passes.  With the test's three steps no
+candidate reaches the piece share (a partition's gamma window is 0.05 wide whatever M_2, and the later
+steps' partitions hold fewer EVs); the selected cases run two:
+
+    python scripts/select_station_case.py 12 16 2     # M_2 512, seed 2
+    python scripts/select_station_case.py 16 16 2     # M_2 768, seed 6
+
+    python scripts/select_station_case.py [n_lo n_bi [Tf]]
+"""
+import os
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+for p in ("incentive-design-mpc_amd", "oracle", "tests"):
+    sys.path.insert(0, os.path.join(ROOT, p))
+
+import lompc_oracle as O  # noqa: E402
+import oracle_c  # noqa: E402
+import station_oracle as SO  # noqa: E402
+import test_gpu_station as T  # noqa: E402
+
+EDGE = 1e-6
+SIZES = (512, 768, 1024, 1536, 2048)
+SEEDS = range(1, 9)
+
+
+def patterns(ps, lm):
+    """Distinct active-set patterns of the per-EV optima of ps's current partition at prices lm."""
+    c = ps.consts
+    full = np.zeros(3 * ps.N)
+    full[: ps.r] = lm[: ps.r]
+    W, _, nf = oracle_c.solve_batch(ps.N, c, full, 0.0, c.y_max - ps.y0)
+    assert nf == 0
+    code = (W <= 1e-12).astype(np.int8) + 2 * (W >= c.w_max - 1e-12).astype(np.int8)
+    return len(np.unique(code, axis=0))
+
+
+def trajectory(n_lo, n_bi, M_2, seed, Tf):
+    c = T.consts(M_2, Tf=Tf, n_lo=n_lo, n_bi=n_bi)
+    np.random.seed(seed)
+    bi = dict(delta=1e3, c_g=1, u_g_max=1, u_b_max=0.3, x_max=0.3, cost_type=1, exp_rate=5)
+    so = SO.OracleStation(n_bi, n_lo, M_2, T.P, c.demand, bi, O.small_consts(), O.large_consts(), "linear-convex", Tf)
+    loops, margin = [], [np.inf]
+    for ps in (so.ps_s, so.ps_l):
+        ps.warm = "state"
+        ps.get_w0_price0 = ps.get_w0_price0_batch  # (the C batch instead of one Python solve per EV)
+        errs = []
+
+        def werr(*a, _f=ps._get_w_err, _e=errs, **k):
+            r = _f(*a, **k)
+            _e.append(r[2])
+            return r
+
+        def solve(w_ref, lr, _f=ps.compute_optimal_prices, _e=errs, _ps=ps):
+            _e.clear()
+            lm, st = _f(w_ref, lr)
+            tol = O.get_robustness_bounds(_ps.N, _ps.consts.delta, _ps.y0_rng, lr)[0]
+            margin[0] = min(margin[0], float(np.min(np.abs(np.array(_e) - tol) / tol)))
+            loops.append(patterns(_ps, lm))
+            return lm, st
+
+        ps._get_w_err, ps.compute_optimal_prices = werr, solve
+    moved = np.zeros(2, dtype=int)
+    t0 = time.perf_counter()
+    for _ in range(Tf):
+        before = (so.idx_s.copy(), so.idx_l.copy(), so.y_s.copy(), so.y_l.copy())
+        so.step()
+        for k, (i0, i1, y0, y1) in enumerate(((before[0], so.idx_s, before[2], so.y_s),
+                                              (before[1], so.idx_l, before[3], so.y_l))):
+            moved[k] += int(np.sum((i0 != i1) & (y1 >= y0)))  # (a re-drawn EV's level falls)
+    dt = time.perf_counter() - t0
+    share = float(np.mean(np.array(loops) >= 2))
+    return dict(loops=len(loops), share=share, moved=moved, ncharged=int(so.ncharged_s + so.ncharged_l),
+                margin=margin[0], seconds=dt, niter_max=int(max(so.logs["niter_s"].max(), so.logs["niter_l"].max())))
+
+
+def main(argv):
+    n_lo, n_bi = (int(argv[0]), int(argv[1])) if len(argv) >= 2 else (12, 16)
+    Tf = int(argv[2]) if len(argv) >= 3 else T.TF
+    for M_2 in SIZES:
+        for seed in SEEDS:
+            r = trajectory(n_lo, n_bi, M_2, seed, Tf)
+            ok = r["share"] >= 0.5 and r["moved"].min() >= 1 and r["ncharged"] > 0 and r["margin"] >= EDGE
+            print(f"n_lo {n_lo} n_bi {n_bi} Tf {Tf} M_2 {M_2} seed {seed}: loops {r['loops']}  >=2-pattern share "
+                  f"{r['share']:.3f}  moved s/l {r['moved'][0]}/{r['moved'][1]}  ncharged {r['ncharged']}  "
+                  f"closest |err - tol| / tol {r['margin']:.3e}  max niter {r['niter_max']}  oracle {r['seconds']:.2f} s  "
+                  f"{'SELECTED' if ok else 'no'}", flush=True)
+            if ok:
+                return 0
+    return 1
+
+
+if __name__ == "__main__":
+    sys.exit(main(sys.argv[1:]))

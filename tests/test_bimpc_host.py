@@ -145,3 +145,29 @@ def test_demand_forecast_restates_reference():
     np.testing.assert_array_equal(d[:24], d[24:48])
     di = medium_term_demand_forecast(24, 1.0, interpolate=True)
     assert di.shape == (48,) and di[1] == 73822 and di[47] == 76068
+
+
+def test_polish_solves_again_after_releasing_a_row():
+    """The active-set polish on an instance where its first solve gives a coupling row a negative
+    multiplier (-1.5e-5): the row is released and the problem solved again before the stationarity of the
+    free variables is judged.  (Judged at once, without the released row's multiplier, a free variable
+    missed the bar by 3.2e-6, the polish gave up and the interior point's iterate was returned: zeros of
+    w_hat at 5e-7, w_hat[:, 0] off by 1.7e-6 — tests/test_gpu_station.py's mid_N16 trajectory, step 1,
+    whose BiMPC instance and dense interior-point solution are tests/golden/bimpc_released_row.json.)
+    The planner's point now equals the oracle's to 1e-9, at the same objective."""
+    import json
+    import os
+
+    with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "bimpc_released_row.json")) as f:
+        d = json.load(f)
+    N, P = d["N"], d["P"]
+    arr = {k: np.array(d[k]) for k in ("Mp_s", "Mp_l", "beta_s", "beta_l", "gamma_sm", "gamma_lm", "demand")}
+    lit = BO.BiMPCLiteral(N, P, d["bi"], CS.theta, CL.theta, CS.w_max, CL.w_max, dict(x0=d["x0"], **arr))
+    bi = BiMPCConstants(1e3, 1, 1, 0.3, 0.3, BiMPCChargingCostType.UNWEIGHTED, 5)
+    b, ws, wl, ug = solve(N, P, bi, BiMPCParameters(arr["Mp_s"], arr["Mp_l"], arr["beta_s"], arr["beta_l"],
+                                                    arr["gamma_sm"], arr["gamma_lm"], d["x0"], arr["demand"]))
+    z, zo = lit.pack(ws, wl, ug), np.array(d["z"])
+    np.testing.assert_allclose(z, zo, rtol=0, atol=1e-9)
+    assert abs(lit.objective(z) - lit.objective(zo)) <= 1e-12 * abs(lit.objective(zo))
+    stat, infeas, comp, dual_inf = lit.kkt(z, b.last_duals)
+    assert stat <= 1e-12 and comp <= 1e-12 and infeas <= 1e-12 and dual_inf == 0.0

@@ -52,23 +52,53 @@ def compare_logs(logs, ol):
         np.testing.assert_allclose(a, b, rtol=0, atol=1e-6 * scale, err_msg=k)
 
 
-@pytest.mark.parametrize("n_lo,n_bi,storage", [(N_LO, N_BI, 0.3), (48, 48, 0.5)], ids=["example", "config5_N48"])
-def test_closed_loop_matches_oracle(gpu, monkeypatch, n_lo, n_bi, storage):
+@pytest.mark.parametrize("n_lo,n_bi,storage,M_2,seed,Tf",
+                         [(N_LO, N_BI, 0.3, 60, 1, TF), (48, 48, 0.5, 60, 1, TF), (12, 16, 0.3, 512, 2, 2), (16, 16, 0.3, 768, 6, 2)],
+                         ids=["example", "config5_N48", "mid_N12", "mid_N16"])
+def test_closed_loop_matches_oracle(gpu, monkeypatch, n_lo, n_bi, storage, M_2, seed, Tf):
     """The example's horizons (12 / 16) and config 5's (48 / 48; storage rate and capacity 0.5,
     as bench.py's station leg: at horizon 48 the example's 0.3 / 0.3 leaves the first BiMPC
-    infeasible)."""
+    infeasible), at M_2 = 60: five EVs per partition.
+
+    mid_N12 / mid_N16: the same loop at mid size, where a partition holds up to a few hundred EVs — the
+    sorted layout's piece boundaries and prefix sums, the perm scatter of w0, plan.update between steps
+    and the re-draws are compared with the oracle over the trajectory; (16, 16) is the route by which the
+    station's own call sequence reaches the <16> kernels.  M_2, seed and Tf were chosen on the oracle
+    alone (scripts/select_station_case.py, CPU): the smallest M_2 from 512 and the first seed of 1..8
+    whose oracle trajectory has >= 2 distinct active-set patterns (each stage at 0, at w_max, interior)
+    among the per-EV optima at the final prices in at least half of its populated (type, partition, step)
+    loops, at least one EV of each type changing partition, a re-draw, and every tested average error at
+    least 1e-6 tol away from tol.  With Tf = 3 no candidate reached the piece share (M_2 = 512, seeds 1..8:
+    0.26-0.43; 768, seeds 1..3: 0.30-0.46 at (12, 16); (16, 16), 512 and 768: 0.23-0.33 — a partition's gamma window is
+    0.05 wide whatever M_2, so most loops hold one piece, and the later steps' partitions fewer EVs); the
+    oracle's time is dominated by its dense BiMPC interior point (about 2.5 s per step whatever M_2, the M_2 = 60
+    cases included), so Tf was lowered to 2.  The script's output for the selected cases:
+
+      n_lo 12 n_bi 16 Tf 2 M_2 512 seed 2: loops 17  >=2-pattern share 0.529  moved s/l 971/1024
+        ncharged 53  closest |err - tol| / tol 2.542e-03  max niter 55  oracle 13.05 s
+      n_lo 16 n_bi 16 Tf 2 M_2 768 seed 6: loops 16  >=2-pattern share 0.500  moved s/l 1523/1536
+        ncharged 13  closest |err - tol| / tol 8.288e-03  max niter 22  oracle 6.71 s
+
+    (seconds with both selections running side by side on a busy host; alone 5.9 s and 6.1 s there, of
+    which the two BiMPC solves take about 5; each case, oracle included, 1.7 s on the MI355X machine).
+    The oracle's price solvers run its warm C batch there (ps.warm = "state", get_w0_price0_batch: the
+    same optima).  mid_N16 failed on its first run (w_hat_s[7, 0] of step 1 off by 1.7e-6): the host
+    BiMPC planner's polish, fixed with it (tests/test_bimpc_host.py)."""
     import station_oracle as SO
 
     monkeypatch.setattr(settings, "PRINT_LEVEL", 0)
-    M_2 = 60
-    c = consts(M_2, n_lo=n_lo, n_bi=n_bi, storage=storage)
-    np.random.seed(1)
+    c = consts(M_2, Tf=Tf, n_lo=n_lo, n_bi=n_bi, storage=storage)
+    np.random.seed(seed)
     cs = ChargingStation(c, device=0)
     logs = cs.simulate()
-    np.random.seed(1)
+    np.random.seed(seed)
     bi = dict(delta=1e3, c_g=1, u_g_max=1, u_b_max=storage, x_max=storage, cost_type=1, exp_rate=5)
-    so = SO.OracleStation(n_bi, n_lo, M_2, P, c.demand, bi, O.small_consts(), O.large_consts(), "linear-convex", TF)
-    for _ in range(TF):
+    so = SO.OracleStation(n_bi, n_lo, M_2, P, c.demand, bi, O.small_consts(), O.large_consts(), "linear-convex", Tf)
+    if M_2 > 60:
+        for ps in (so.ps_s, so.ps_l):
+            ps.warm = "state"
+            ps.get_w0_price0 = ps.get_w0_price0_batch
+    for _ in range(Tf):
         so.step()
     compare_logs(logs, so.logs)
     # logs hold the count before the last state update (_update_logs precedes _update_state, :181-183)

@@ -88,7 +88,14 @@ int lompc_set_mode(lompc_ctx* ctx, int mode);
  *   lmbd_r dev  [S]      robustness price >= 0           (lompc.py:80)
  *   w_ref  dev  [S, N]   reference w for the A_bar error (price_solver.py:196), or NULL
  *   gamma_ref dev [S]    central gamma per set (gamma_sc, price_solver.py:76), or NULL
- *                        (NULL = y_max / 2); only used by LOMPC_MODE_DIRECT */
+ *                        (NULL = y_max / 2); only used by LOMPC_MODE_DIRECT
+ * Price magnitude: the engine's certificate tolerance, 1e-11 (1 + c N^2 w_max + slope + theta^2), does
+ * not grow with the prices.  Measured (tests/test_gpu_plan_prices.py): single components up to 3.9e5
+ * theta (what a capped price loop reaches), lambda_3 * 1e6 and per-entry scales 1e-8 .. 1e3 are solved
+ * and certified at every horizon; with EVERY price at 3.9e5 theta * U(0, 1) correct optima are reported
+ * LOMPC_QP_FAILED at N <= 16 (certified from N = 24); dense prices of 1e7 theta and above are reported
+ * FAILED at every horizon.  Past these limits the engine fails loudly (N_FAILED, LOMPC_QP_FAILED): the
+ * same test asserts that every EV with status OK or REPAIRED is inside the 1e-9 bar. */
 int lompc_set_params(lompc_ctx* ctx, int64_t S, const double* lmbd,
                      const double* lmbd_r, const double* w_ref,
                      const double* gamma_ref, void* stream);

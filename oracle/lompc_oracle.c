@@ -18,6 +18,7 @@
  * Same algorithm and tolerances as the Python oracle; cross-checked against it
  * and against the 50-digit golden vectors in tests/.
  */
+#include <float.h>
 #include <math.h>
 #include <stdint.h>
 #include <stdlib.h>
@@ -27,6 +28,8 @@
 #endif
 
 #define OMAXN 128
+/* margin of the release test over one coordinate's forward error bound (lompc_oracle.py) */
+#define RELEASE_ULPS 8.0
 
 typedef struct {
   int N, small;
@@ -144,14 +147,9 @@ static int solve_one(const ocfg* c, const double* H, const double* g, double* w,
   const int N = c->N;
   double wh[OMAXN], p[OMAXN], rhs[OMAXN], M[OMAXN * OMAXN];
   int F[OMAXN];
-  double gmax = 0.0, hmax = 0.0;
-  for (int j = 0; j < N; ++j) {
-    if (fabs(g[j]) > gmax) gmax = fabs(g[j]);
-    for (int k = 0; k < N; ++k)
-      if (fabs(H[j * N + k]) > hmax) hmax = fabs(H[j * N + k]);
-  }
-  double scale = 1.0 + gmax + hmax * c->w_max * N + fabs(c->slopes[c->m - 1]);
-  const double tol = 1e-12 * scale;
+  /* release / termination tolerance, per coordinate: RELEASE_ULPS (N + 2) eps times the magnitudes
+   * that enter (Hw + g)_j + slope (lompc_oracle.py solve_state); nothing of the other coordinates */
+  const double noise = RELEASE_ULPS * (double)(N + 2) * DBL_EPSILON;
   for (int j = 0; j < N; ++j) {
     if (!warm) st[j] = 0;
     w[j] = (st[j] & 1) ? 0.5 * (c->knots[(st[j] - 1) >> 1] + c->knots[(st[j] + 1) >> 1]) : c->knots[st[j] >> 1];
@@ -189,15 +187,24 @@ static int solve_one(const ocfg* c, const double* H, const double* g, double* w,
     }
     if (blk < 0) {
       memcpy(w, wh, N * sizeof(double));
-      double best = tol;
+      double best = 0.0;
       int bj = -1, bd = 0;
       for (int j = 0; j < N; ++j) {
         if (st[j] & 1) continue;
-        double r = g[j];
-        for (int k = 0; k < N; ++k) r += H[j * N + k] * w[k];
+        double r = g[j], mag = fabs(g[j]);
+        for (int k = 0; k < N; ++k) {
+          r += H[j * N + k] * w[k];
+          mag += fabs(H[j * N + k]) * fabs(w[k]);
+        }
         int k = st[j] >> 1;
-        if (k < c->m && -r - c->slopes[k] > best) { best = -r - c->slopes[k]; bj = j; bd = 1; }
-        if (k > 0 && r + c->slopes[k - 1] > best) { best = r + c->slopes[k - 1]; bj = j; bd = -1; }
+        if (k < c->m) {
+          double v = -r - c->slopes[k];
+          if (v > best && v > noise * (mag + fabs(c->slopes[k]))) { best = v; bj = j; bd = 1; }
+        }
+        if (k > 0) {
+          double v = r + c->slopes[k - 1];
+          if (v > best && v > noise * (mag + fabs(c->slopes[k - 1]))) { best = v; bj = j; bd = -1; }
+        }
       }
       if (bj < 0) {
         if (iters) *iters = it + 1;

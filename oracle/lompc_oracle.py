@@ -55,6 +55,10 @@ PRICE_SOLVER_EPS_TOL = 0.01
 PWL_KNOTS_REL = (0.0, 0.125, 0.5, 0.75, 1.0)
 PWL_SLOPES_REL = (0.0, 1.0, 1.5, 2.0)
 
+# Margin of the active set's release test over the forward error bound of one coordinate's gradient
+# (solve_state; the same rule in lompc_oracle.c).
+RELEASE_ULPS = 8.0
+
 
 @dataclass
 class OracleConstants:
@@ -173,10 +177,13 @@ class OracleLoMPC:
         nk = len(self.knots)
         st = np.zeros(N, dtype=np.int64)  # all fixed at knot 0 (w = 0, feasible)
         w = np.zeros(N)
-        scale = 1.0 + np.max(np.abs(g)) + np.max(np.abs(H)) * self.w_max * N
-        if len(self.slopes):
-            scale += np.max(np.abs(self.slopes))
-        tol = 1e-12 * scale
+        # Release / termination tolerance, per coordinate: a multiplier counts as wrong-signed only
+        # beyond the rounding noise of its own evaluation, RELEASE_ULPS (N + 2) eps times the
+        # magnitudes that enter (Hw + g)_j + slope (an (N + 2)-term sum's forward error bound, times a
+        # margin for the error of w itself).  It does not grow with the largest entry of H or g
+        # elsewhere, so one huge price leaves the other coordinates' test as sharp as without it.
+        absH, absg = np.abs(H), np.abs(g)
+        noise = RELEASE_ULPS * (N + 2) * np.finfo(np.float64).eps
         for _ in range(max_iter):
             w_hat = self._subproblem(H, g, st)
             p = w_hat - w
@@ -198,18 +205,19 @@ class OracleLoMPC:
             if blk < 0:
                 w = w_hat
                 r = H @ w + g
-                best, bj, bdir = tol, -1, 0
+                mag = absH @ np.abs(w) + absg
+                best, bj, bdir = 0.0, -1, 0
                 for j in range(N):
                     if st[j] % 2 == 1:
                         continue
                     k = st[j] // 2
                     if k < nk - 1:
                         v = -r[j] - self.slopes[k]
-                        if v > best:
+                        if v > best and v > noise * (mag[j] + abs(self.slopes[k])):
                             best, bj, bdir = v, j, +1
                     if k > 0:
                         v = r[j] + self.slopes[k - 1]
-                        if v > best:
+                        if v > best and v > noise * (mag[j] + abs(self.slopes[k - 1])):
                             best, bj, bdir = v, j, -1
                 if bj < 0:
                     return w, st
@@ -295,10 +303,44 @@ def _coord_residual(wj, neg_rj, knots, slopes, ktol):
 # --------------------------------------------------------------------------
 # 50-digit certificate / refinement
 # --------------------------------------------------------------------------
-def refine_mp(lompc: OracleLoMPC, st, lmbd, lmbd_r, gamma, dps=50):
+def _solve_spd_mp(M, b):
+    """x with M x = b for a symmetric positive definite M (lists of mpf): LDL' without pivoting."""
+    n = len(b)
+    L = [[None] * n for _ in range(n)]
+    d = [None] * n
+    for j in range(n):
+        Lj = L[j]
+        s = M[j][j]
+        for k in range(j):
+            s -= Lj[k] * Lj[k] * d[k]
+        d[j] = s
+        for i in range(j + 1, n):
+            Li = L[i]
+            t = M[i][j]
+            for k in range(j):
+                t -= Li[k] * Lj[k] * d[k]
+            Li[j] = t / s
+    x = list(b)
+    for i in range(n):
+        Li = L[i]
+        for k in range(i):
+            x[i] -= Li[k] * x[k]
+    for i in range(n):
+        x[i] /= d[i]
+    for i in range(n - 1, -1, -1):
+        for k in range(i + 1, n):
+            x[i] -= L[k][i] * x[k]
+    return x
+
+
+def refine_mp(lompc: OracleLoMPC, st, lmbd, lmbd_r, gamma, dps=50, full=False):
     """Solve the working set ``st`` exactly at ``dps`` digits from the fp64
     inputs and certify optimality there.  Returns (w_mp as fp64 array,
-    relative KKT residual at dps digits, min strict-interior slack)."""
+    relative KKT residual at dps digits, min strict-interior slack).
+
+    A multiplier or a distance to a segment's end below 10^(8 - dps) (relative: eight guard digits over
+    the arithmetic's own rounding) is an exact tie, reported as 0: its sign at ``dps`` digits is
+    rounding.  full: also the worst violated coordinate as (j, state to move it to) or None."""
     import mpmath as mp
 
     mp.mp.dps = dps
@@ -309,14 +351,14 @@ def refine_mp(lompc: OracleLoMPC, st, lmbd, lmbd_r, gamma, dps=50):
     lr, ga = mp.mpf(float(lmbd_r)), mp.mpf(float(gamma))
     qs = 3 * th / (4 * wmax)
     # H = 2 de th^2 A'A + diag(...)   (A'A)_{jk} = N - max(j,k)
-    H = mp.matrix(N, N)
+    cc = 2 * de * th ** 2
+    col = [cc * (N - k) for k in range(N)]
+    H = [[col[max(j, k)] for k in range(N)] for j in range(N)]
     for j in range(N):
-        for k in range(N):
-            H[j, k] = 2 * de * th ** 2 * (N - max(j, k))
-        H[j, j] += 2 * lr * th ** 2 + 2 * qs * lm[2 * N + j]
+        H[j][j] += 2 * lr * th ** 2 + 2 * qs * lm[2 * N + j]
         if lompc.ev_type == "small":
-            H[j, j] += 2 * th ** 2 / (mp.mpf(0.9) ** 2)
-    g = [th * (lm[j] - lm[N + j]) - 2 * de * th ** 2 * ga * (N - j) for j in range(N)]
+            H[j][j] += 2 * th ** 2 / (mp.mpf(0.9) ** 2)
+    g = [th * (lm[j] - lm[N + j]) - cc * ga * (N - j) for j in range(N)]
     if lompc.ev_type == "small":
         knots = [mp.mpf(0), wmax]
         slopes = [mp.mpf(0)]
@@ -331,42 +373,73 @@ def refine_mp(lompc: OracleLoMPC, st, lmbd, lmbd_r, gamma, dps=50):
     for j in fixed:
         w[j] = knots[int(st[j]) // 2]
     if free:
-        nf = len(free)
-        Hff = mp.matrix(nf, nf)
-        rhs = mp.matrix(nf, 1)
-        for a, j in enumerate(free):
+        rhs = []
+        for j in free:
             s = g[j] + slopes[(int(st[j]) - 1) // 2]
+            Hj = H[j]
             for k in fixed:
-                s += H[j, k] * w[k]
-            rhs[a] = -s
-            for b, k in enumerate(free):
-                Hff[a, b] = H[j, k]
-        x = mp.lu_solve(Hff, rhs)
+                s += Hj[k] * w[k]
+            rhs.append(-s)
+        x = _solve_spd_mp([[H[j][k] for k in free] for j in free], rhs)
         for a, j in enumerate(free):
             w[j] = x[a]
-    r = [sum(H[j, k] * w[k] for k in range(N)) + g[j] for j in range(N)]
+    r = [mp.fdot(H[j], w) + g[j] for j in range(N)]
     scale = 1 + max(abs(x) for x in g) + 2 * de * th ** 2 * N * wmax * N
+    tie = mp.mpf(10) ** (8 - dps)
     res = mp.mpf(0)
     slack = mp.inf
     m = len(slopes)
+    worst, worst_v = None, mp.mpf(0)
+
+    def snap(v):
+        return mp.mpf(0) if abs(v) <= tie else v
+
     for j in range(N):
         if st[j] % 2 == 1:
             k = (int(st[j]) - 1) // 2
             res = max(res, abs(-r[j] - slopes[k]))
-            slack = min(slack, (w[j] - knots[k]) / wmax, (knots[k + 1] - w[j]) / wmax)
+            below, above = snap((w[j] - knots[k]) / wmax), snap((knots[k + 1] - w[j]) / wmax)
+            slack = min(slack, below, above)
+            if -below > worst_v:
+                worst, worst_v = (j, 2 * k), -below
+            if -above > worst_v:
+                worst, worst_v = (j, 2 * k + 2), -above
         else:
             k = int(st[j]) // 2
             lo = None if k == 0 else slopes[k - 1]
             hi = None if k == m else slopes[k]
             v = -r[j]
             if lo is not None:
-                res = max(res, lo - v)
-                slack = min(slack, (v - lo) / scale)
+                d = snap((v - lo) / scale)
+                res = max(res, -d * scale)
+                slack = min(slack, d)
+                if -d > worst_v:
+                    worst, worst_v = (j, 2 * k - 1), -d
             if hi is not None:
-                res = max(res, v - hi)
-                slack = min(slack, (hi - v) / scale)
+                d = snap((hi - v) / scale)
+                res = max(res, -d * scale)
+                slack = min(slack, d)
+                if -d > worst_v:
+                    worst, worst_v = (j, 2 * k + 1), -d
     w64 = np.array([float(x) for x in w])
+    if full:
+        return w64, float(res / scale), float(slack), worst
     return w64, float(res / scale), float(slack)
+
+
+def certify_mp(lompc: OracleLoMPC, st, lmbd, lmbd_r, gamma, dps=50):
+    """The optimum itself at ``dps`` digits: ``refine_mp`` from working set ``st``, and while a coordinate
+    is wrong-signed or outside its segment there, move the worst one to the neighbouring state and solve
+    again (an active set finished in extended precision).  From an fp64 oracle's final working set this
+    moves only coordinates whose multiplier fp64 could not sign.
+    Returns (w_mp as fp64 array, residual, slack, the final state, the number of moves)."""
+    st = np.array(st, dtype=np.int64)
+    for moves in range(4 * lompc.N + 1):
+        w, res, slack, worst = refine_mp(lompc, st, lmbd, lmbd_r, gamma, dps, full=True)
+        if worst is None:
+            return w, res, slack, st, moves
+        st[worst[0]] = worst[1]
+    raise RuntimeError("certify_mp did not terminate")
 
 
 # --------------------------------------------------------------------------

@@ -18,6 +18,9 @@ counts, prices, the prices before / after regularisation, the dual cost decrease
 loop, and get_w0_price0 (price_solver.py:272-285) at the capped loop's final prices.  These are
 checker outputs (no reference code ran: cvxpy is absent); the trajectory inputs
 come from the GPU run, the expected outputs only from the oracle.
+
+Without the station's dump the second command alone re-derives the expected outputs from the inputs the
+committed fixture already stores (after a change of the oracle: same inputs, new checker outputs).
 """
 from __future__ import annotations
 
@@ -50,17 +53,33 @@ def oracle_loop(c, y0, w_ref, prev, lmbd_r):
     return po, lm, st
 
 
+def inputs(cls, name):
+    """The case's inputs: from the station's dump when it is there, else the ones the committed fixture
+    already stores (the expected outputs are then re-derived from the same inputs)."""
+    if os.path.exists(os.path.join(SRC, name + ".npz")):
+        d = np.load(os.path.join(SRC, name + ".npz"))
+        nx = np.load(os.path.join(SRC, name + "_next.npz"))
+        return d, nx, int(len(nx["y0"]))
+    arr = np.load(os.path.join(HERE, "price_loop_long.npz"), allow_pickle=False)
+    with open(os.path.join(HERE, "price_loop_long.json")) as f:
+        m = json.load(f)["cases"][cls]
+    d = {k: np.array(arr[f"{cls}_{k}"]) for k in ("y0", "w_ref", "prev_prices", "pstats")}
+    d.update(kind=m["kind"], lmbd_r=m["lmbd_r"], iter=m["iter_gpu_trajectory"])
+    nx = {"y0": np.array(arr[f"{cls}_next_y0"]), "w_ref": np.array(arr[f"{cls}_next_w_ref"])}
+    return d, nx, int(m["next_n_evs_station"])
+
+
 def main():
     out, meta = {}, {}
     for cls, name in CASES.items():
-        d = np.load(os.path.join(SRC, name + ".npz"))
-        nx = np.load(os.path.join(SRC, name + "_next.npz"))
+        d, nx, n_station = inputs(cls, name)
         kind = str(d["kind"])
         c = O.large_consts() if kind == "Large" else O.small_consts()
         lr = float(d["lmbd_r"])
         ny = nx["y0"]
-        sel = np.unique(np.round(np.linspace(0, len(ny) - 1, NEXT_EVS)).astype(np.int64))
-        ny = np.ascontiguousarray(ny[sel])
+        if len(ny) > NEXT_EVS:
+            sel = np.unique(np.round(np.linspace(0, len(ny) - 1, NEXT_EVS)).astype(np.int64))
+            ny = np.ascontiguousarray(ny[sel])
         t0 = time.perf_counter()
         po, lm, st = oracle_loop(c, d["y0"], d["w_ref"], d["prev_prices"], lr)
         po2, lm2, st2 = oracle_loop(c, ny, nx["w_ref"], lm[: po.r], lr)
@@ -74,14 +93,14 @@ def main():
                     p + "next_dec_actual": st2["dual_cost_decrease_actual"],
                     p + "next_dec_pred": st2["dual_cost_decrease_predicted"], p + "w0": w0})
         meta[cls] = {"source": name, "kind": kind, "lmbd_r": lr, "n_evs": int(len(d["y0"])),
-                     "next_n_evs": int(len(ny)), "next_n_evs_station": int(len(nx["y0"])),
+                     "next_n_evs": int(len(ny)), "next_n_evs_station": n_station,
                      "iter": int(st["iter"]), "iter_gpu_trajectory": int(d["iter"]),
                      "price_before_reg": float(st["price_before_reg"]), "price_after_reg": float(st["price_after_reg"]),
                      "next_iter": int(st2["iter"]), "next_price_before_reg": float(st2["price_before_reg"]),
                      "next_price_after_reg": float(st2["price_after_reg"]), "price0_mean": float(p0),
                      "max_price_over_theta": float(np.abs(lm).max() / c.theta), "oracle_seconds": round(dt, 1)}
         print(cls, meta[cls], flush=True)
-    np.savez(os.path.join(HERE, "price_loop_long.npz"), **out)
+    np.savez_compressed(os.path.join(HERE, "price_loop_long.npz"), **out)
     with open(os.path.join(HERE, "price_loop_long.json"), "w") as f:
         json.dump({"doc": __doc__.split("\n\n")[2].replace("\n", " "), "cases": meta}, f, indent=1)
 

@@ -98,16 +98,23 @@ class Batch:
                 if layout == "sorted":
                     g = np.sort(g)
                 parts.append(g)
+        lm = np.stack([np.concatenate([c.theta * rng.random((P, 3 * N)) for c in self.cs]) for _ in range(K)])
+        big = int(np.argmax(sizes))
+        lm[:, 2, :N] = 0.0        # small type: the 63-EV set, no charging price (upper bound active)
+        lm[:, P + big, :N] = 0.0  # large type: its largest set
+        mask = np.tile(np.resize([0.0, 1.0, 0.0, 1.0, 1.0], P), 2)
+        lr = 0.2 * rng.random((K, 2 * P)) * mask
+        self.take(parts, lm, lr)
+
+    def take(self, parts, lm, lr):
+        """The batch from prepared data: parts, each set's gamma (P sets per type, the small type's first);
+        lm (K, 2P, 3N) and lr (K, 2P), the runs' prices.  w_ref is drawn from self.rng."""
+        N, P = self.N, self.P
         self.gn = np.concatenate(parts)
         self.off = np.concatenate([[0], np.cumsum([len(x) for x in parts])]).astype(np.int64)
         self.B = int(self.off[-1])
-        self.lm = np.stack([np.concatenate([c.theta * rng.random((P, 3 * N)) for c in self.cs]) for _ in range(K)])
-        big = int(np.argmax(sizes))
-        self.lm[:, 2, :N] = 0.0        # small type: the 63-EV set, no charging price (upper bound active)
-        self.lm[:, P + big, :N] = 0.0  # large type: its largest set
-        mask = np.tile(np.resize([0.0, 1.0, 0.0, 1.0, 1.0], P), 2)
-        self.lr = 0.2 * rng.random((K, 2 * P)) * mask
-        self.wr = np.concatenate([c.w_max * rng.random((P, N)) for c in self.cs])
+        self.lm, self.lr = lm, lr
+        self.wr = np.concatenate([c.w_max * self.rng.random((P, N)) for c in self.cs])
         dev = "cuda:0"
         self.g = torch.as_tensor(self.gn, device=dev)
         self.lm_d, self.lr_d = torch.as_tensor(self.lm, device=dev), torch.as_tensor(self.lr, device=dev)

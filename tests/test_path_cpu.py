@@ -98,3 +98,40 @@ def test_path_cpu_golden(golden):
         assert o["info"][3] == 0
         np.testing.assert_allclose(o["w"], case["w"], atol=TOL_W, rtol=0)
         np.testing.assert_allclose(o["cost"], case["cost"], rtol=1e-9, atol=1e-9)
+
+
+FAMILY_NS = [1, 2, 5, 12, 13, 16, 24, 32, 48, 64]
+
+
+@pytest.mark.parametrize("N", FAMILY_NS)
+def test_path_cpu_price_families(N):
+    """The host path engine against the dense oracle on every price family (tests/price_families.py:
+    flat, tied, zero, ramped, two-level, one huge component, scaled prices), both EV types, lmbd_r = 0 and
+    1.5 N delta, at the GPU bars (|dw| <= 1e-9, cost 1e-9 relative).  Prints each family's piece count and
+    individually solved EVs (the GPU test prints its REPAIRED counts beside them)."""
+    import price_families as PF
+
+    cs = [O.small_consts(), O.large_consts()]
+    gs = [PF.gammas(N, t) for t in ("small", "large")]
+    g = np.concatenate([gs[0], gs[0], gs[1], gs[1]])
+    off = np.arange(5, dtype=np.int64) * PF.N_GAMMA
+    worst_w = worst_c = 0.0
+    for fam in PF.FAMILIES:
+        lm = np.stack([PF.prices(fam, N, t) for t in ("small", "small", "large", "large")])
+        lr = np.array(PF.lmbd_rs(N, "small") + PF.lmbd_rs(N, "large"))
+        o = oracle_c.path_run(N, cs, [2, 2], lm, lr, g, off)
+        print(f"N={N} {fam}: pieces {o['info'][0]}, certified cells {o['info'][1]}, solved individually "
+              f"{o['info'][2]} of {g.size}, failed {o['info'][3]}")
+        assert o["info"][3] == 0, fam
+        for s in range(4):
+            a, b = off[s], off[s + 1]
+            wo, co, nf = oracle_c.solve_batch(N, cs[s // 2], lm[s], lr[s], g[a:b])
+            assert nf == 0, (fam, s)
+            dw = float(np.max(np.abs(o["w"][a:b] - wo)))
+            dc = float(np.max(np.abs(o["cost"][a:b] - co) / (1e-9 + 1e-9 * np.abs(co))))
+            worst_w, worst_c = max(worst_w, dw), max(worst_c, dc)
+            assert dw <= TOL_W, (fam, s, dw)
+            assert dc <= 1.0, (fam, s, dc)
+            assert o["set_stats"][s][0] == b - a and o["set_stats"][s][6] == 0 and o["set_stats"][s][7] == 0
+            np.testing.assert_allclose(o["set_sum_w"][s], wo.sum(0), rtol=1e-10, atol=1e-9)
+    print(f"N={N}: largest |dw| {worst_w:.2e}, largest cost deviation {worst_c:.2e} of its bar")

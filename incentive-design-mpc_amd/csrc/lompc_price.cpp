@@ -60,14 +60,19 @@ struct TriSolve {
   }
 };
 
+// theta^2 / (2 eps m) from which every reduced solve is refined (PriceQP::solve).  The shipped
+// constants give 500 (small) and 1000 (large), which certify without; delta = 1e-4 gives 2.5e5.
+constexpr double NNQP_ILL = 4000.0;
+
 // Q = 2P = 2 eps I + U A_bar^-1 U' / m ;  row i of U is u[i] e_{i mod N}'.
 // A_bar = A'A + kappa I (price_solver.py:191-192).
 struct PriceQP {
   int N = 0, r = 0;
   double eps = 0.0, m = 0.0, kappa = 0.0;
-  std::vector<double> u, E, s, v;
+  std::vector<double> u, E, s, v, rq, rz;
   std::vector<int> st;  // stage of row i (i mod N, precomputed: integer division dominated the loops)
   TriSolve Ab, Gf;
+  bool ill = false;  // theta^2 / m > NNQP_ILL 2 eps: every reduced solve gets a refinement step (solve)
 
   bool init(int N_, int r_, double theta, double w_max, double m_, double kappa_, double eps_, const double* w) {
     N = N_;
@@ -86,6 +91,11 @@ struct PriceQP {
     E.assign(N, kappa);
     s.assign(N, 0.0);
     v.assign(N, 0.0);
+    ill = theta * theta > NNQP_ILL * 2.0 * eps * m;
+    if (ill) {
+      rq.assign(r, 0.0);
+      rz.assign(r, 0.0);
+    }
     return Ab.factor(N, 1.0, E.data());
   }
 
@@ -115,6 +125,20 @@ struct PriceQP {
     for (int i = 0; i < r; ++i) z[i] = F[i] ? h * (q[i] - u[i] * s[st[i]]) : 0.0;
     return true;
   }
+
+  // solveF, and where the QP is ill-conditioned (ill) one step of iterative refinement on it: the
+  // Woodbury form subtracts two terms of q's magnitude to leave 2 eps z, so its error in Q z + q grows
+  // like theta^2 / (2 eps m) = 1 / (4 eps delta) and reaches 1e-8 at delta = 1e-4, where it decides
+  // the signs the active-set methods branch on and fails their certificate (1e-12 after the step).
+  bool solve(const std::vector<char>& F, const double* q, double* z) {
+    if (!solveF(F, q, z)) return false;
+    if (!ill) return true;
+    mulQ(z, rq.data());
+    for (int i = 0; i < r; ++i) rq[i] = F[i] ? rq[i] + q[i] : 0.0;
+    if (!solveF(F, rq.data(), rz.data())) return false;
+    for (int i = 0; i < r; ++i) z[i] += rz[i];
+    return true;
+  }
 };
 
 // KKT residual of x for min 1/2 x'Qx + q'x, x >= 0 (mu = Qx + q).
@@ -127,16 +151,20 @@ double kkt_res(const std::vector<double>& x, const std::vector<double>& mu) {
   return res;
 }
 
+// Steps of iterative refinement a converged free set gets before its certificate decides (one
+// suffices at delta = 1e-4: KKT residual 1e-8 -> 1e-12; nnqp_wave, lompc_pricewave.hpp, has the same).
+constexpr int NNQP_REFINE = 2;
+
 // Exact non-negative QP: PDAS from the warm free set, primal active set as fallback.
 int nnqp(PriceQP& P, const double* q, const double* x_warm, double* x_out, double tol, int* iters) {
   const int r = P.r;
   std::vector<char> F(r, 0), Fn(r, 0);
-  std::vector<double> z(r), mu(r), x(r, 0.0);
+  std::vector<double> z(r), mu(r), x(r, 0.0), Fz(r);
   for (int i = 0; i < r; ++i) F[i] = x_warm && x_warm[i] > 0.0;
   int it = 0;
   // primal-dual active set (Hintermueller-Ito-Kunisch)
   for (int k = 0; k < 64; ++k, ++it) {
-    if (!P.solveF(F, q, z.data())) return LOMPC_ERR_NOT_CONVERGED;
+    if (!P.solve(F, q, z.data())) return LOMPC_ERR_NOT_CONVERGED;
     P.mulQ(z.data(), mu.data());
     bool same = true;
     for (int i = 0; i < r; ++i) {
@@ -145,6 +173,16 @@ int nnqp(PriceQP& P, const double* q, const double* x_warm, double* x_out, doubl
       same = same && (Fn[i] == F[i]);
     }
     if (same) {
+      // below NNQP_ILL the same loss can still pass the certificate's tolerance: the residual mu_F is
+      // then rounding on a fixed free set, which refinement on that set removes; only taken when the
+      // certificate would refuse
+      for (int rf = 0; rf < NNQP_REFINE && kkt_res(z, mu) > tol; ++rf) {
+        for (int i = 0; i < r; ++i) x[i] = F[i] ? mu[i] : 0.0;
+        if (!P.solveF(F, x.data(), Fz.data())) break;
+        for (int i = 0; i < r; ++i) z[i] += Fz[i];
+        P.mulQ(z.data(), mu.data());
+        for (int i = 0; i < r; ++i) mu[i] += q[i];
+      }
       if (kkt_res(z, mu) <= tol) {
         std::copy(z.begin(), z.end(), x_out);
         if (iters) *iters = it + 1;
@@ -158,7 +196,7 @@ int nnqp(PriceQP& P, const double* q, const double* x_warm, double* x_out, doubl
   std::fill(F.begin(), F.end(), 0);
   std::fill(x.begin(), x.end(), 0.0);
   for (int k = 0; k < 64 * r + 64; ++k, ++it) {
-    if (!P.solveF(F, q, z.data())) return LOMPC_ERR_NOT_CONVERGED;
+    if (!P.solve(F, q, z.data())) return LOMPC_ERR_NOT_CONVERGED;
     double alpha = 1.0;
     int blk = -1;
     for (int i = 0; i < r; ++i)

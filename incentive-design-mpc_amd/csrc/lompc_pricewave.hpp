@@ -77,7 +77,8 @@ struct PriceQPW {
   int N, nb, lane;
   double u[3];
   double eps, m, kappa;
-  Tri Ab;  // factor of A_bar = A'A + kappa I
+  bool ill;  // theta^2 / m > 4000 (2 eps), lompc_price.cpp NNQP_ILL: every reduced solve is refined (solve)
+  Tri Ab;    // factor of A_bar = A'A + kappa I
 
   // ab: the factor of A_bar = A'A + kappa I when known (it depends on kappa and N only: the device
   // loop computes it at its first step and keeps it), else null
@@ -89,6 +90,7 @@ struct PriceQPW {
     eps = eps_;
     m = m_;
     kappa = kappa_;
+    ill = theta * theta > 4000.0 * 2.0 * eps_ * m_;
     const double q_s = 3.0 * theta / (4.0 * w_max);  // lompc.py:67
     const bool act = lane < N;
     u[0] = act ? theta : 0.0;   // Dphi rows, lompc.py:179-187
@@ -124,6 +126,20 @@ struct PriceQPW {
     const double h = -0.5 / eps;
 #pragma unroll
     for (int k = 0; k < 3; ++k) z[k] = F[k] ? h * fma(-u[k], s, q[k]) : 0.0;
+  }
+
+  // solveF, and for an ill-conditioned QP one step of iterative refinement on it (PriceQP::solve,
+  // lompc_price.cpp: the Woodbury form's error in Q z + q grows like 1 / (4 eps delta))
+  __device__ __forceinline__ void solve(const bool (&F)[3], const double (&q)[3], double (&z)[3]) const {
+    solveF(F, q, z);
+    if (!ill) return;
+    double rq[3], rz[3];
+    mulQ(z, rq);
+#pragma unroll
+    for (int k = 0; k < 3; ++k) rq[k] = F[k] ? rq[k] + q[k] : 0.0;
+    solveF(F, rq, rz);
+#pragma unroll
+    for (int k = 0; k < 3; ++k) z[k] += rz[k];
   }
 
   __device__ __forceinline__ double kkt(const double (&x)[3], const double (&mu)[3]) const {
@@ -168,7 +184,7 @@ __device__ __forceinline__ bool nnqp_wave(const PriceQPW& P, const double (&q)[3
   for (int k = 0; k < 3; ++k) F[k] = P.has(k) && xw[k] > 0.0;
   double z[3];
   for (int it = 0; it < 64; ++it) {
-    P.solveF(F, q, z);
+    P.solve(F, q, z);
     P.mulQ(z, mu);
     bool Fn[3], diff = false;
 #pragma unroll
@@ -178,7 +194,22 @@ __device__ __forceinline__ bool nnqp_wave(const PriceQPW& P, const double (&q)[3
       diff |= Fn[k] != F[k];
     }
     if (!__any(diff)) {
-      if (P.kkt(z, mu) <= tol) {
+      // iterative refinement on the converged free set when the certificate would refuse (the host's
+      // NNQP_REFINE, lompc_price.cpp: solveF's Woodbury form loses like 1 / (4 eps delta))
+      double res = P.kkt(z, mu);
+      for (int rf = 0; rf < 2 && res > tol; ++rf) {
+        double rr[3], dz[3];
+#pragma unroll
+        for (int k = 0; k < 3; ++k) rr[k] = F[k] ? mu[k] : 0.0;
+        P.solveF(F, rr, dz);
+#pragma unroll
+        for (int k = 0; k < 3; ++k) z[k] += dz[k];
+        P.mulQ(z, mu);
+#pragma unroll
+        for (int k = 0; k < 3; ++k) mu[k] += q[k];
+        res = P.kkt(z, mu);
+      }
+      if (res <= tol) {
 #pragma unroll
         for (int k = 0; k < 3; ++k) x[k] = z[k];
         return true;
@@ -196,7 +227,7 @@ __device__ __forceinline__ bool nnqp_wave(const PriceQPW& P, const double (&q)[3
     x[k] = 0.0;
   }
   for (int it = 0; it < 64 * r + 64; ++it) {
-    P.solveF(F, q, z);
+    P.solve(F, q, z);
     double ratio[3];
     bool blocking[3];
 #pragma unroll

@@ -471,7 +471,12 @@ int lompc_price_regularize(int N, int r, double theta, double w_max, const doubl
  *   *dual_cost_decrease = (lmbd'P lmbd + q'lmbd) - (x'Px + q'x)      (:236, :244-245)
  *   *iterations = active-set iterations used (may be NULL)
  * Exact (finite active-set method), KKT-certified; LOMPC_ERR_NOT_CONVERGED
- * otherwise (cvxpy SolverError). */
+ * otherwise (cvxpy SolverError).  The certificate's tolerance is 1e-11 (1 + max |q|); the reduced
+ * solves' error grows like theta^2 / (2 eps_reg m) = 1 / (4 eps_reg delta) (1e-8 at delta = 1e-4),
+ * so above 4000 every reduced solve takes one step of iterative refinement, and below it a
+ * converged free set that misses the certificate takes up to two before the certificate decides
+ * (the device loop's step, lompc_pricewave.hpp, does the same).  The shipped constants (500 and
+ * 1000) certify without either. */
 int lompc_price_step(int N, int r, double theta, double w_max, double m, double kappa,
                      double eps_reg, const double* w_ref, const double* w, const double* lmbd,
                      double* lmbd_next, double* dual_cost_decrease, int* iterations);

@@ -106,21 +106,29 @@ class Batch:
         lr = 0.2 * rng.random((K, 2 * P)) * mask
         self.take(parts, lm, lr)
 
-    def take(self, parts, lm, lr):
-        """The batch from prepared data: parts, each set's gamma (P sets per type, the small type's first);
-        lm (K, 2P, 3N) and lr (K, 2P), the runs' prices.  w_ref is drawn from self.rng."""
+    def take(self, parts, lm, lr, device=True):
+        """The batch from prepared data: parts, each set's gamma (P sets per context of self.cs, in their
+        order: the small type's first); lm (K, S, 3N) and lr (K, S), the runs' prices, S = len(cs) P.
+        w_ref is drawn from self.rng.  device = False: the host arrays only (CPU scripts)."""
         N, P = self.N, self.P
         self.gn = np.concatenate(parts)
         self.off = np.concatenate([[0], np.cumsum([len(x) for x in parts])]).astype(np.int64)
         self.B = int(self.off[-1])
         self.lm, self.lr = lm, lr
         self.wr = np.concatenate([c.w_max * self.rng.random((P, N)) for c in self.cs])
+        self.strides = (self.S * 3 * N, self.S)
+        self._oracle = {}
+        if not device:
+            return
         dev = "cuda:0"
         self.g = torch.as_tensor(self.gn, device=dev)
         self.lm_d, self.lr_d = torch.as_tensor(self.lm, device=dev), torch.as_tensor(self.lr, device=dev)
         self.wr_d = torch.as_tensor(self.wr, device=dev)
-        self.strides = (2 * P * 3 * N, 2 * P)
-        self._oracle = {}
+
+    @property
+    def S(self):
+        """Parameter sets of the batch: P per context."""
+        return len(self.cs) * self.P
 
     def consts_of(self, s):
         return self.cs[s // self.P]
@@ -131,7 +139,7 @@ class Batch:
             return self._oracle[k]
         g = self.gn if gn is None else gn
         W, C = np.zeros((self.B, self.N)), np.zeros(self.B)
-        for s in range(2 * self.P):
+        for s in range(self.S):
             a, b = self.off[s], self.off[s + 1]
             if b > a:
                 W[a:b], C[a:b], nf = oracle_c.solve_batch(self.N, self.consts_of(s), self.lm[k, s], float(self.lr[k, s]), g[a:b])
@@ -143,7 +151,7 @@ class Batch:
     def oracle_sets(self, k, gn=None):
         """The oracle's per-set sums at run k: (sum w (S, N), sum w0, sum price0, sum cost)."""
         W, C = self.oracle(k, gn)
-        N, S = self.N, 2 * self.P
+        N, S = self.N, self.S
         sw, p0, sc = np.zeros((S, N)), np.zeros(S), np.zeros(S)
         for s in range(S):
             a, b = self.off[s], self.off[s + 1]
@@ -205,7 +213,7 @@ def sets_vs_oracle(dev, bt, k, sw, st, cost=True, gn=None):
 def sets_vs_own_rows(dev, bt, w, cost, sw, st):
     """A rows form's set reductions against the sums of its own per-EV outputs (check_reductions of
     test_gpu_pipeline.py: rtol 1e-11, atol 1e-9)."""
-    for s in range(2 * bt.P):
+    for s in range(bt.S):
         a, b = bt.off[s], bt.off[s + 1]
         ref = w[a:b].sum(0)
         dev.add("sums vs own rows", np.abs(sw[s] - ref), 1e-9 + 1e-11 * np.abs(ref))

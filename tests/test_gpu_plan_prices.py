@@ -119,7 +119,7 @@ def ok_or_repaired(status):
 
 
 def repaired_by_set(bt, status):
-    return {bt.label(s): int(np.sum(status[bt.off[s]:bt.off[s + 1]] == ST.LOMPC_QP_REPAIRED)) for s in range(2 * bt.P)}
+    return {bt.label(s): int(np.sum(status[bt.off[s]:bt.off[s + 1]] == ST.LOMPC_QP_REPAIRED)) for s in range(bt.S)}
 
 
 def repaired_span(bt, status, big):
@@ -136,24 +136,27 @@ def repaired_span(bt, status, big):
     return spans
 
 
-def host_individual(bt):
-    """EVs the host path engine (oracle/path_cpu.cpp) solves individually at run 0's prices, per set label."""
-    if bt._host is not None:
-        return bt._host
-    out = bt._host = {}
-    for s in range(2 * bt.P):
+def host_individual(bt, cells=0):
+    """EVs the host path engine (oracle/path_cpu.cpp) solves individually at run 0's prices, per set label.
+    cells: gamma cells per set (0: the host engine's choice from each set's own size)."""
+    if bt._host is None:
+        bt._host = {}
+    if cells in bt._host:
+        return bt._host[cells]
+    out = bt._host[cells] = {}
+    for s in range(bt.S):
         a, b = bt.off[s], bt.off[s + 1]
         o = oracle_c.path_run(bt.N, [bt.consts_of(s)], [1], bt.lm[0, s][None, :], bt.lr[0, s:s + 1], bt.gn[a:b],
-                              np.array([0, b - a], dtype=np.int64), want_cost=False)
+                              np.array([0, b - a], dtype=np.int64), cells=cells, want_cost=False)
         out[bt.label(s)] = int(o["info"][2])
     return out
 
 
-def print_repaired(name, bt, nrep):
+def print_repaired(name, bt, nrep, cells=0):
     """Run 0's REPAIRED count per set (nrep: (S,)) beside the host path engine's individually solved EVs."""
-    host = host_individual(bt)
+    host = host_individual(bt, cells)
     print(f"{name}: REPAIRED (device) / solved individually (host) per set: "
-          + ", ".join(f"{bt.label(s)} {int(nrep[s])}/{host[bt.label(s)]}" for s in range(2 * bt.P)
+          + ", ".join(f"{bt.label(s)} {int(nrep[s])}/{host[bt.label(s)]}" for s in range(bt.S)
                       if nrep[s] or host[bt.label(s)]))
 
 
@@ -355,7 +358,7 @@ def direct_vs_oracle(bt, dev, loud=False):
     N, P = bt.N, bt.P
     W, C = bt.oracle(0)
     w, cost, status = np.zeros((bt.B, N)), np.zeros(bt.B), np.zeros(bt.B, dtype=np.int8)
-    sw, st = np.zeros((2 * P, N)), np.zeros((2 * P, ST.LOMPC_SET_STATS))
+    sw, st = np.zeros((bt.S, N)), np.zeros((bt.S, ST.LOMPC_SET_STATS))
     for t, c in enumerate(bt.cs):
         lo = LoMPC(N, LoMPCConstants(c.delta, c.theta, c.y_max, c.w_max, c.ev_type), device=0, mode="direct")
         a, b = int(bt.off[t * P]), int(bt.off[(t + 1) * P])

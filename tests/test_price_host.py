@@ -26,11 +26,12 @@ def c_price_step(N, r, c, m, kappa, w_ref, w, lmbd, eps=PO.EPS_REG):
     return out, dec.value, it.value
 
 
-def cases(n):
+def cases(n, consts=None):
+    """consts: (small, large) constant sets instead of the shipped pair (the same draws)."""
     rng = np.random.default_rng(123)
     for k in range(n):
         ev = "small" if k % 2 == 0 else "large"
-        c = O.small_consts() if ev == "small" else O.large_consts()
+        c = (consts or (O.small_consts(), O.large_consts()))[k % 2]
         N = (12, 24, 48)[k % 3]
         price = ("linear-convex", "linear")[(k // 3) % 2]
         r = 3 * N if price == "linear-convex" else 2 * N
@@ -60,6 +61,40 @@ def test_price_step_matches_dense_oracle(case):
     np.testing.assert_allclose(x, xo, rtol=0, atol=1e-8 * (1 + np.max(np.abs(xo))))
     assert abs(dec - deco) <= 1e-8 * max(1.0, abs(deco))
     assert dec >= -1e-9 * max(1.0, abs(deco))  # a descent step never increases the majorizer
+
+
+# delta = 1e-4 (theta 0.1 and 1000): theta^2 / m = 1 / (2 delta) = 5000 against 2 eps = 0.02 on the diagonal of
+# Q.  The Woodbury reduced solve alone leaves a KKT residual of 1e-8 there, 100 times the certificate's
+# tolerance (LOMPC_ERR_NOT_CONVERGED at every step of a price loop); with a step of iterative refinement per
+# reduced solve (PriceQP::solve) it is 1e-12.
+SMALL_DELTA = (O.OracleConstants(1e-4, 0.1, 0.75, 0.01, "small"), O.OracleConstants(1e-4, 1000.0, 0.75, 0.01, "large"))
+
+
+@pytest.mark.parametrize("case", list(cases(24, SMALL_DELTA)), ids=lambda c: f"{c[0]}-N{c[2]}-r{c[3]}")
+def test_price_step_small_delta_matches_dense_oracle(case):
+    """test_price_step_matches_dense_oracle at delta = 1e-4: the step certifies (rc 0) and its answer is a
+    KKT point of the reference's dense problem at the same 1e-9 (1 + max |q|).  The dense oracle's own
+    accuracy bounds the two comparisons with it at this conditioning, so their bars come from it:
+    * x: two points with KKT residuals rho_e, rho_o (max norm, price_qp_kkt) of a QP whose Hessian 2P has
+      smallest eigenvalue >= 2 eps are at most sqrt(r) (rho_e + rho_o) / (2 eps) apart;
+    * the decrease: both sides are differences of the r-term dense sums l'Pl, q'l, x'Px, q'x; 1e-13 of the
+      sum of their magnitudes is the forward error bound of evaluating them in fp64 (r eps = 3e-14)."""
+    ev, c, N, r, lmbd_r, w, w_ref, lmbd = case
+    m = 2 * c.delta * c.theta ** 2
+    A = np.tril(np.ones((N, N)))
+    _, A_bar_inv = O.w_inner_product_metric(A, c.delta, lmbd_r)
+    x, dec, _ = c_price_step(N, r, c, m, lmbd_r / c.delta, w_ref, w, lmbd)
+    xo, deco = PO.price_step(N, r, c.theta, c.w_max, m, A_bar_inv, w_ref, w, lmbd)
+    P, q, _ = PO.price_qp_data(N, r, c.theta, c.w_max, m, A_bar_inv, w_ref, w, lmbd)
+    rho_e, rho_o = PO.price_qp_kkt(P, q, x), PO.price_qp_kkt(P, q, xo)
+    assert np.all(x >= 0) and rho_e <= 1e-9 * (1.0 + np.max(np.abs(q)))
+    bar_x = np.sqrt(r) * (rho_e + rho_o) / (2 * PO.EPS_REG)
+    mags = abs(lmbd @ P @ lmbd) + abs(q @ lmbd) + abs(x @ P @ x) + abs(q @ x)
+    print(f"{ev} N={N} r={r}: KKT engine {rho_e:.2e} oracle {rho_o:.2e}; |dx| {np.max(np.abs(x - xo)):.2e} (bar {bar_x:.2e}); "
+          f"|ddec| {abs(dec - deco):.2e} (bar {1e-13 * mags:.2e})")
+    assert np.max(np.abs(x - xo)) <= bar_x
+    assert abs(dec - deco) <= 1e-13 * mags
+    assert dec >= -1e-13 * mags  # a descent step never increases the majorizer
 
 
 def test_price_step_fixed_point():

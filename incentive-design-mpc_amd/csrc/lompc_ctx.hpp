@@ -99,6 +99,7 @@ struct lompc_plan {
   QPConst* d_q = nullptr;       // [nctx]
   int64_t B = 0, S = 0;
   int G = 0;                    // gamma cells per set (k_path waves per set)
+  int cap = 0;                  // piece slots of one set the evaluation stages in LDS (eval_cap)
   int nblk = 0;                 // k_eval workgroups (blocks of one set's EVs)
   int n_cu = 0;
   bool close = false;           // the sets' closing inside k_eval (no k_finalize launch)

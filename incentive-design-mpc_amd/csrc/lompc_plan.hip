@@ -35,7 +35,10 @@
 #include <chrono>
 #include <cmath>
 #include <cstdlib>
+#include <map>
+#include <mutex>
 #include <type_traits>
+#include <utility>
 
 #include "lompc_ctx.hpp"
 #include "lompc_loopstep.hpp"
@@ -2533,6 +2536,63 @@ size_t eval_lds(int N, int G, int cap) {
   return std::max(stage, (size_t)2 * EVAL_WAVES * FIN_W * sizeof(double));  // (close mode: red / rep)
 }
 
+// The dynamic LDS the evaluation kernels of horizon N may ask for: a workgroup's LDS on the device less
+// the largest static LDS of k_eval (both close modes), k_evals and k_step (any of them may run a plan).
+// Queried once per (device, instantiation) in the process.
+static int eval_lds_room(lompc_plan* p, int device, int N, size_t* room) {
+  static std::mutex mu;
+  static std::map<std::pair<int, int>, size_t> known;
+  const int inst = (N == 12 || N == 16 || N == 24 || N == 48) ? N : 0;
+  std::lock_guard<std::mutex> lock(mu);
+  const auto it = known.find({device, inst});
+  if (it != known.end()) {
+    *room = it->second;
+    return LOMPC_OK;
+  }
+  int limit = 0;
+  HIPCHK(p, hipDeviceGetAttribute(&limit, hipDeviceAttributeMaxSharedMemoryPerBlock, device));
+  const void* const kern[4] = {(const void*)eval_kernel<false>(N), (const void*)eval_kernel<true>(N),
+                               (const void*)evals_kernel(N), (const void*)step_kernel(N)};
+  size_t fixed = 0;
+  for (const void* f : kern) {
+    hipFuncAttributes at;
+    HIPCHK(p, hipFuncGetAttributes(&at, f));
+    fixed = std::max(fixed, (size_t)at.sharedSizeBytes);
+  }
+  *room = (size_t)limit > fixed ? (size_t)limit - fixed : 0;
+  // the runtime's own account must agree that a workgroup asking for all of it is resident (a request
+  // past the limit is not refused at the launch: it aborts the queue)
+  for (const void* f : kern) {
+    int occ = 0;
+    while (*room >= 1024) {
+      HIPCHK(p, hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, f, EVAL_EVS, *room));
+      if (occ >= 1) break;
+      *room -= 1024;
+    }
+  }
+  known[{device, inst}] = *room;
+  return LOMPC_OK;
+}
+
+// The piece slots of one set that the evaluation stages in LDS (EvalArgs::cap): LQ_PIECE_CAP, or all of
+// the set's G LQ_PPL when that is fewer, lowered by whole cells until eval_lds fits beside the kernels'
+// static LDS (long horizons with many cells: 16 (N + 1) + 92 bytes per slot and 12 per cell).  The EVs
+// of the cells left unstaged take the certified individual re-solve, as those past LQ_PIECE_CAP do.
+static int eval_cap(lompc_plan* p, int device, int N, int G, int* cap) {
+  size_t room = 0;
+  const int rc = eval_lds_room(p, device, N, &room);
+  if (rc) return rc;
+  int c = std::min(LQ_PIECE_CAP, G * LQ_PPL);
+  while (c > LQ_PPL && eval_lds(N, G, c) > room) c -= LQ_PPL;
+  if (eval_lds(N, G, c) > room) {
+    p->err = "plan: horizon " + std::to_string(N) + " with " + std::to_string(G) +
+             " cells per set does not fit a workgroup's LDS (" + std::to_string(room) + " bytes for the evaluation)";
+    return LOMPC_ERR_UNSUPPORTED;
+  }
+  *cap = c;
+  return LOMPC_OK;
+}
+
 // events of one profiled dispatch (null events when kernel k is not profiled)
 int plan_prof_begin(lompc_plan* p, int k, hipEvent_t* e0, hipEvent_t* e1) {
   *e0 = *e1 = nullptr;
@@ -2598,7 +2658,8 @@ int lq_plan_prepare(lompc_plan* p, int nctx, lompc_ctx* const* ctxs, const int64
     if (p->n_cu < 1) p->n_cu = 1;
   }
   LQ_PREP_MARK(1);
-  const int cap = std::min(LQ_PIECE_CAP, G * LQ_PPL);
+  int cap = 0;
+  if (const int rc_cap = eval_cap(p, ctxs[0]->device, N, G, &cap)) return rc_cap;
   const int64_t occ_key = (int64_t)N * 4096 + cap;
   if (p->eval_occ_key != occ_key) {  // k_eval workgroups resident per CU (either variant may run)
     int occ0 = 0, occ1 = 0;
@@ -2677,6 +2738,7 @@ int lq_plan_prepare(lompc_plan* p, int nctx, lompc_ctx* const* ctxs, const int64
   p->B = B;
   p->S = S;
   p->G = G;
+  p->cap = cap;
   p->nblk = (int)nblk;
   p->n_empty = (int)n_empty;
   p->d_stats = p->d_stats_own;
@@ -2880,7 +2942,7 @@ void eval_args(lompc_plan* p, const double* lmbd, const double* lmbd_r, double* 
   a.fail_idx = p->d_fail_idx;
   a.w_rsrc_ok = (p->B * (int64_t)N * 8) <= LQ_DROP_OFF ? 1 : 0;
   a.w_bytes = a.w_rsrc_ok ? (int)(p->B * (int64_t)N * 8) : 0;
-  a.cap = std::min(LQ_PIECE_CAP, p->G * LQ_PPL);
+  a.cap = p->cap;
   a.nblk = p->nblk;
   a.skip = p->skip;
   r = FinalArgs{};
@@ -3324,7 +3386,7 @@ int stepped_setup(lompc_plan* p, hipStream_t st, bool wide) {
   const int N = p->N;
   const int64_t S = p->S, G = p->G, ncell = S * G, B = p->B;
   const bool stg = wide && evals_stg_ok(p);
-  const int cap = std::min(stg ? LQ_EVALS_CAP : LQ_PIECE_CAP, p->G * LQ_PPL);
+  const int cap = stg ? std::min(LQ_EVALS_CAP, p->G * LQ_PPL) : p->cap;
   const int64_t okey = ((int64_t)N * 4096 + G) * 2 + (stg ? 1 : 0);
   if (z.occ_key != okey) {
     if (stg)
@@ -3508,8 +3570,7 @@ int lq_run_steps_stepped(lompc_plan* p, const double* lmbd, int64_t lmbd_stride,
       r.status = nullptr;
     }
   };
-  const int cap = std::min(LQ_PIECE_CAP, p->G * LQ_PPL);
-  const size_t lds = eval_lds(N, p->G, cap);
+  const size_t lds = eval_lds(N, p->G, p->cap);
   const StepKernel kern = step_kernel(N);
   // (split runs without w output take the batched launches one run per group too: their evaluation
   // sums the certified pieces instead of rows, so only these kernels give the wide form's bits)

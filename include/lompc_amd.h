@@ -189,9 +189,12 @@ typedef struct lompc_plan lompc_plan;
 #define LOMPC_PLAN_CLOSE_IN_FINALIZE 32 /* runs without w output close their sets in the k_finalize
                                            launch like runs with w (default: inside k_eval); the
                                            A/B form of the close-mode parity tests */
-/* gamma cells per set (1 .. 1024) instead of the plan's own choice: flags | LOMPC_PLAN_CELLS(g).
- * The answer does not depend on it (every piece is certified); it trades per-cell tracking
- * latency against cold starts. */
+/* gamma cells per set (1 .. 1024, at every horizon; more: LOMPC_ERR_INVALID_ARG at create) instead of
+ * the plan's own choice: flags | LOMPC_PLAN_CELLS(g).  The answer does not depend on it (every piece
+ * is certified); it trades per-cell tracking latency against cold starts.  The
+ * evaluation stages the pieces of a set's first 16 cells in LDS — fewer where N and g are both large
+ * (N = 64 from 41 cells, N = 59 from 911: 15) — and re-solves the EVs of the other cells one by one, so
+ * counts far above 16 are exact but slow. */
 #define LOMPC_PLAN_CELLS_SHIFT 20
 #define LOMPC_PLAN_CELLS(g) ((int)(g) << LOMPC_PLAN_CELLS_SHIFT)
 

@@ -64,8 +64,12 @@ def test_path_cpu_matches_dense_oracle(N):
 
 
 def test_path_cpu_cells_and_bounds():
-    """The answer does not depend on the cell count (1 / 8 / 64 cells), and gammas at 0 and y_max and
-    invalid ones (NaN, negative, above y_max: counted, NaN outputs) are handled as on the device."""
+    """The answer does not depend on the cell count, and gammas at 0 and y_max and invalid ones (NaN,
+    negative, above y_max: counted, NaN outputs) are handled as on the device.  Cells: 1, 8 and 64, one past
+    every count at which the device kernels change path (3: no multiple of k_step's 4; 17: past k_eval's 16
+    staged cells; 65, 513: past a wave / a workgroup of cell loads) and the maximum, 1024 — more cells than
+    EVs, so most cells are empty and every window edge falls between neighbouring EVs.  Every count against
+    the dense oracle at the file's bars, and against the one-cell run to 1e-12."""
     rng = np.random.default_rng(7)
     N = 24
     c = O.large_consts()
@@ -74,12 +78,13 @@ def test_path_cpu_cells_and_bounds():
     lm = c.theta * rng.random((1, 3 * N))
     lr = np.array([0.1])
     ref = None
-    for cells in (1, 8, 64):
+    for cells in (1, 3, 8, 17, 64, 65, 513, 1024):
         o = oracle_c.path_run(N, [c], [1], lm, lr, g, off, cells=cells)
+        assert o["info"][3] == 0, cells
         if ref is None:
             ref = o
-            _check(o, [c], [0], off, g, lm, lr, np.zeros((1, N)), N)
-        np.testing.assert_allclose(o["w"], ref["w"], atol=1e-12, rtol=0)
+        _check(o, [c], [0], off, g, lm, lr, np.zeros((1, N)), N)
+        np.testing.assert_allclose(o["w"], ref["w"], atol=1e-12, rtol=0, err_msg=str(cells))
     g2 = g.copy()
     g2[[3, 4, 5]] = [np.nan, -1.0, 2.0]
     o = oracle_c.path_run(N, [c], [1], lm, lr, g2, off)

@@ -95,6 +95,13 @@ __device__ unsigned long long g_lstamps[64 * 16];  // k_loop_iter's phase sums (
 #ifndef EVAL_PASSES
 #define EVAL_PASSES 2                      // k_eval: EVs per thread, at most
 #endif
+#ifndef LQ_EVAL_WV_SCALAR
+#define LQ_EVAL_WV_SCALAR 1  // eval_block: the wave index as a scalar (0: as the compiler derives it from threadIdx)
+#endif
+#ifndef LQ_EVALS_KARGS
+#define LQ_EVALS_KARGS 1  // k_evals: its arguments re-read from the kernel argument segment in every run (0: held in
+                          // scalar registers across the runs' loop, which spills them to vector lanes)
+#endif
 #define EVAL_MAXB (EVAL_EVS * EVAL_PASSES)  // k_eval: EVs per workgroup, at most
 #ifndef LQ_PIECE_CAP
 #define LQ_PIECE_CAP 128                   // k_eval: piece slots of one set staged in LDS (more: re-solved)
@@ -1125,7 +1132,9 @@ __device__ __forceinline__ void eval_block(const EvalArgs& a, const int blk, con
   int tid_ = (int)threadIdx.x;
   if (ro.launder) asm volatile("" : "+v"(tid_));  // (k_evals: lane-derived indices recomputed every run, not
                                                   // hoisted out of its loop and spilled)
-  const int tid = tid_, lane = tid & 63, wv = tid >> 6;
+  // (the wave index through readfirstlane: what follows from it — the wave's rows, its pass counts, its record
+  // slots — is then scalar: branches on it are scalar branches, not exec masks)
+  const int tid = tid_, lane = tid & 63, wv = LQ_EVAL_WV_SCALAR ? __builtin_amdgcn_readfirstlane(tid >> 6) : tid >> 6;
   const int4 info = a.blk[blk];
   const int rb = ro.rec + blk;  // this block's record (k_evals: in its run's record slot)
   // per-EV outputs (k_evals with per-run outputs: at the run's offset)
@@ -1281,12 +1290,15 @@ __device__ __forceinline__ void eval_block(const EvalArgs& a, const int blk, con
   LQ_STAMPE(1);
   // ---- lane = EV: piece, scalar outputs; EVs no certified piece covers listed for the
   //      individual re-solve (counted as pending failures until then)
-  const double ym = q.y_max, wm = q.w_max;
+  // (w_max canonical here, once: fmin quiets its operands, and the compiler otherwise does so per row batch)
+  const double ym = q.y_max, wm = __builtin_canonicalize(q.w_max);
   const double tt = q.theta * q.theta;
   const double cscale = (double)G / (whi - wlo);
   const double fxs = 0x1p40 / (whi - wlo);  // (CLOSE) gamma - wlo in units of the window / 2^40
   double acc_cost = 0.0, acc_p0 = 0.0, acc_err = 0.0;
-  int n_ok = 0, n_fail = 0, n_inv = 0, nlist = 0;
+  // (wave-uniform counts: ballot + popcount per pass, no per-lane counters to reduce; the wave's re-solved
+  // EVs are its list's length)
+  int n_ok = 0, n_inv = 0, nlist = 0;
   bool inv_rows = false;  // (wave-uniform) some row of this wave has an invalid gamma
   const int mxc = STG ? stg_meta[0] : s_mx;  // (block-uniform) the set's largest cell piece count: no piece end past it is read
   // one pass of the lookup: this thread's EV h
@@ -1295,7 +1307,11 @@ __device__ __forceinline__ void eval_block(const EvalArgs& a, const int blk, con
   // stores then follow the row stores instead of holding them back); per pass the piece and flags
   int pk[EVAL_PASSES];
   unsigned pf[EVAL_PASSES];  // bit 0: cov, bit 1: act && !valid
-  auto lookup_key = [&](const int h) {
+  // MX > 0: the set's largest cell piece count (mxc) as a constant, so the compare and select chains below run
+  // over MX ends and not the table's LQ_PPL (a cell's count is at most mxc: the dropped terms are all false);
+  // MX = 0: any mxc
+  auto lookup_key_mx = [&](auto mx_t, const int h) {
+    constexpr int MX = decltype(mx_t)::value, KE = MX ? MX : LQ_PPL;
     const int i = start + brow(h);
     const bool act = bact(h);
     const double g = gh[h];
@@ -1305,15 +1321,15 @@ __device__ __forceinline__ void eval_block(const EvalArgs& a, const int blk, con
     const int kb = STG ? s_pre[c] : c * LQ_PPL, ke = kb + nc;  // the cell's pieces [kb, ke), ascending gamma
     double ge[LQ_PPL];
 #pragma unroll
-    for (int k = 0; k < LQ_PPL; ++k)
-      ge[k] = (k < mxc && !LQ_DIAG_NOLOOKUP) ? s_ge[STG ? kb + k : k * Gs + min(c, Gs - 1)] : 0.0;
+    for (int k = 0; k < KE; ++k)
+      ge[k] = ((MX || k < mxc) && !LQ_DIAG_NOLOOKUP) ? s_ge[STG ? kb + k : k * Gs + min(c, Gs - 1)] : 0.0;
     const double glo_c = s_lo[c];
     int key = kb;  // piece = number of piece ends below g (every end read at once, no loop)
     double gend = ge[0];
 #pragma unroll
-    for (int k = 0; k + 1 < LQ_PPL; ++k) key += (k + 1 < nc && g > ge[k]) ? 1 : 0;
+    for (int k = 0; k + 1 < KE; ++k) key += (k + 1 < nc && g > ge[k]) ? 1 : 0;
 #pragma unroll
-    for (int k = 1; k < LQ_PPL; ++k) gend = nc == k + 1 ? ge[k] : gend;  // the last piece's end
+    for (int k = 1; k < KE; ++k) gend = nc == k + 1 ? ge[k] : gend;  // the last piece's end
     const bool cov = LQ_DIAG_NOLOOKUP ? valid && ke > kb  // (diagnostic timing builds: the cell's first piece)
                                       : valid && ke > kb && (STG || ke <= np) && g >= glo_c && g <= gend;
     pk[h] = key;
@@ -1327,17 +1343,27 @@ __device__ __forceinline__ void eval_block(const EvalArgs& a, const int blk, con
     if (valid && !cov) {
       st_wt4(a.fail_idx + (size_t)rb * EVAL_MAXB + 64 * EVAL_PASSES * wv + nlist +
                  __popcll(need & ((1ull << lane) - 1ull)), i);
-      ++n_fail;
     }
     nlist += __popcll(need);
+  };
+  const int mxu = __builtin_amdgcn_readfirstlane(mxc);
+  auto lookup_key = [&](const int h) {  // (a wave-uniform switch)
+    switch (mxu) {
+      case 1: lookup_key_mx(std::integral_constant<int, 1>{}, h); break;
+      case 2: lookup_key_mx(std::integral_constant<int, 2>{}, h); break;
+      case 3: lookup_key_mx(std::integral_constant<int, 3>{}, h); break;
+      case 4: lookup_key_mx(std::integral_constant<int, 4>{}, h); break;
+      default: lookup_key_mx(std::integral_constant<int, 0>{}, h); break;
+    }
   };
   auto lookup_out = [&](const int h) {
     const int i = start + brow(h);
     const double g = gh[h];
     const int key = pk[h];
     const bool cov = (pf[h] & 1u) != 0u;
+    n_inv += __popcll(__ballot((pf[h] & 2u) != 0u));
+    n_ok += __popcll(__ballot(pf[h] == 1u));
     if ((pf[h] & 2u) != 0u) {
-      ++n_inv;
       if (acost) st_ev8(acost + i, NAN);
       if (aw0) st_ev8(aw0 + i, NAN);
       if (astatus) astatus[i] = LOMPC_QP_INVALID;
@@ -1356,7 +1382,6 @@ __device__ __forceinline__ void eval_block(const EvalArgs& a, const int blk, con
       acc_cost += cst;
       acc_p0 += p0;
       acc_err = fmax(acc_err, er);
-      ++n_ok;
       if (acost) st_ev8(acost + i, cst);
       if (aw0) st_ev8(aw0 + i, w0v);
       if (astatus) astatus[i] = LOMPC_QP_OK;
@@ -1396,19 +1421,18 @@ __device__ __forceinline__ void eval_block(const EvalArgs& a, const int blk, con
   double* const accw_w = accw_all + wv * astr;
   // per-wave totals of the scalar outputs
   auto wave_record = [&]() {
-    double tot[4] = {acc_cost, acc_p0, (double)n_ok, 0.0};
+    double tot[2] = {acc_cost, acc_p0};
     lqw::wave_totals(tot, 64);
-    const double mx = sqrt(lqw::wave_max(acc_err, 64));  // (sqrt is monotone: max of the roots)
-    double cnt[2] = {(double)n_fail, (double)n_inv};
-    lqw::wave_totals(cnt, 64);
+    // (without want_err every lane's error is 0: no scan; sqrt is monotone: max of the roots)
+    const double mx = a.want_err ? sqrt(lqw::wave_max(acc_err, 64)) : 0.0;
     if (lane == 0) {
       red_w[PX_COST] = tot[0];
       red_w[PX_PRICE0] = tot[1];
       red_w[PX_MAX_ERR] = mx;
-      red_w[PX_N_OK] = tot[2];
-      red_w[PX_N_REPAIRED] = tot[3];
-      red_w[PX_N_FAILED] = cnt[0];
-      red_w[PX_N_INVALID] = cnt[1];
+      red_w[PX_N_OK] = (double)n_ok;
+      red_w[PX_N_REPAIRED] = 0.0;
+      red_w[PX_N_FAILED] = (double)nlist;
+      red_w[PX_N_INVALID] = (double)n_inv;
     }
   };
   // the workgroup record (fixed-order combination of the waves'), by the threads of `lanes`
@@ -1489,9 +1513,16 @@ __device__ __forceinline__ void eval_block(const EvalArgs& a, const int blk, con
   const bool fast = aw && a.w_rsrc_ok;
   const __amdgpu_buffer_rsrc_t rs =
       __builtin_amdgcn_make_buffer_rsrc(aw, (short)0, aw ? a.w_bytes : 0, 0x00020000);
+  // (LDS through 32-bit address-space pointers: the piece rows' and the keys' addresses are 32-bit
+  // multiply-adds and shifts, not 64-bit ones)
+  typedef double lds_d2v __attribute__((ext_vector_type(2)));
+  typedef __attribute__((address_space(3))) const lds_d2v lds_cd2;
+  typedef __attribute__((address_space(3))) const double lds_cd;
+  typedef __attribute__((address_space(3))) const int lds_ci;
   auto row_segment = [&](const int r0b, const int nrows) {
-    const int* sk = s_k + r0b;
-    const double* sg = s_g + r0b;
+    lds_ci* sk = (lds_ci*)(s_k + r0b);
+    lds_cd* sg = (lds_cd*)(s_g + r0b);
+    lds_cd2* sab = (lds_cd2*)s_ab;
     const int rbase = start + r0b;
     const int vb = rlane ? ((rbase + rr) * N + t0) * 8 : LQ_DROP_OFF;  // row rr of the segment
     int kk[RU];
@@ -1502,31 +1533,36 @@ __device__ __forceinline__ void eval_block(const EvalArgs& a, const int blk, con
       kk[j] = sk[rc];
       gg[j] = sg[rc];
     }
-    for (int r0 = 0; r0 < nrows; r0 += RU * R) {
-      double2 u0[RU], u1[RU];
+    // the batches r0 = rb, rb + RU R, ... < re.  FULL (every row of the batch exists and is written: no
+    // per-row masks) and FAST (w through the descriptor: one address register, immediate offsets) are
+    // wave-uniform and chosen per run of batches, so a run's loop carries neither test
+    auto batches = [&](auto full_t, auto fast_t, const int rb, const int re) {
+      constexpr bool FULL = decltype(full_t)::value, FAST = decltype(fast_t)::value;
+      for (int r0 = rb; r0 < re; r0 += RU * R) {
+        double2 u0[RU], u1[RU];
 #pragma unroll
-      for (int j = 0; j < RU; ++j) {
-        if (LQ_DIAG_NOROWLDS) {  // (diagnostic timing builds: no LDS reads in the rows)
-          u0[j] = make_double2(1e-3 * kk[j], 1e-3);
-          u1[j] = make_double2(2e-3 * kk[j], 1e-3);
-        } else {
-          u0[j] = s_ab[kk[j] * NS + col];  // stages t0, t0 + 1 (abx)
-          u1[j] = V == 2 ? s_ab[kk[j] * NS + (N >> 1) + col] : make_double2(0.0, 0.0);
+        for (int j = 0; j < RU; ++j) {
+          if (LQ_DIAG_NOROWLDS) {  // (diagnostic timing builds: no LDS reads in the rows)
+            u0[j] = make_double2(1e-3 * kk[j], 1e-3);
+            u1[j] = make_double2(2e-3 * kk[j], 1e-3);
+          } else {
+            const lds_d2v p0 = sab[kk[j] * NS + col];  // stages t0, t0 + 1 (abx)
+            u0[j] = make_double2(p0.x, p0.y);
+            u1[j] = make_double2(0.0, 0.0);
+            if (V == 2) {
+              const lds_d2v p1 = sab[kk[j] * NS + (N >> 1) + col];
+              u1[j] = make_double2(p1.x, p1.y);
+            }
+          }
         }
-      }
-      int kn[RU];  // the next batch's keys and gammas (software pipeline: one LDS round per batch)
-      double gn[RU];
+        int kn[RU];  // the next batch's keys and gammas (software pipeline: one LDS round per batch)
+        double gn[RU];
 #pragma unroll
-      for (int j = 0; j < RU; ++j) {
-        const int rc = min(r0 + (RU + j) * R + rr, nrows - 1);
-        kn[j] = sk[rc];
-        gn[j] = sg[rc];
-      }
-      // a batch's row math and stores; FULL (every row of the batch exists and is written: no
-      // per-row masks) and FAST (w through the descriptor: one address register, immediate
-      // offsets) are wave-uniform and specialised so the common case has no exec-mask change
-      auto rows = [&](auto full_t, auto fast_t) {
-        constexpr bool FULL = decltype(full_t)::value, FAST = decltype(fast_t)::value;
+        for (int j = 0; j < RU; ++j) {
+          const int rc = min(r0 + (RU + j) * R + rr, nrows - 1);
+          kn[j] = sk[rc];
+          gn[j] = sg[rc];
+        }
 #pragma unroll
         for (int j = 0; j < RU; ++j) {
           const double x0 = clampw(fma(u0[j].y, gg[j], u0[j].x), wm);
@@ -1547,27 +1583,37 @@ __device__ __forceinline__ void eval_block(const EvalArgs& a, const int blk, con
             }
           }
         }
-      };
-      using T_ = std::true_type;
-      using F_ = std::false_type;
-      bool full = r0 + RU * R <= nrows;  // wave-uniform
-      if constexpr (CLOSE) {  // a batch with a row left to the re-solve takes the masked path
+#pragma unroll
+        for (int j = 0; j < RU; ++j) {
+          kk[j] = kn[j];
+          gg[j] = gn[j];
+        }
+      }
+    };
+    using T_ = std::true_type;
+    using F_ = std::false_type;
+    if constexpr (CLOSE) {  // a batch with a row left to the re-solve takes the masked path: chosen per batch
+      for (int r0 = 0; r0 < nrows; r0 += RU * R) {
         bool drop = false;
 #pragma unroll
         for (int j = 0; j < RU; ++j) drop |= kk[j] == ZD;
-        full = full && !__any(drop);
+        const bool full = r0 + RU * R <= nrows && !__any(drop);  // wave-uniform
+        if (full) {
+          if (fast) batches(T_{}, T_{}, r0, r0 + 1);
+          else batches(T_{}, F_{}, r0, r0 + 1);
+        } else {
+          if (fast) batches(F_{}, T_{}, r0, r0 + 1);
+          else batches(F_{}, F_{}, r0, r0 + 1);
+        }
       }
-      if (full) {
-        if (fast) rows(T_{}, T_{});
-        else rows(T_{}, F_{});
+    } else {  // the full batches, then the one partial batch (each lane: the same rows in the same order)
+      const int nfull = nrows - nrows % (RU * R);
+      if (fast) {
+        batches(T_{}, T_{}, 0, nfull);
+        if (nfull < nrows) batches(F_{}, T_{}, nfull, nrows);
       } else {
-        if (fast) rows(F_{}, T_{});
-        else rows(F_{}, F_{});
-      }
-#pragma unroll
-      for (int j = 0; j < RU; ++j) {
-        kk[j] = kn[j];
-        gg[j] = gn[j];
+        batches(T_{}, F_{}, 0, nfull);
+        if (nfull < nrows) batches(F_{}, F_{}, nfull, nrows);
       }
     }
     // rows of invalid EVs (gamma outside [0, y_max] or NaN): NaN, written after the loop's
@@ -1596,7 +1642,7 @@ __device__ __forceinline__ void eval_block(const EvalArgs& a, const int blk, con
       __builtin_amdgcn_wave_barrier();  // this wave's own rows in LDS: in order
       any_inv = inv_rows;
       const int r0b = STG ? sg0 + 64 * h : EVAL_EVS * h + 64 * wv;
-      const int nh = STG ? min(64, sgn - 64 * h) : max(0, min(64, end - start - r0b));  // wave-uniform
+      const int nh = __builtin_amdgcn_readfirstlane(STG ? min(64, sgn - 64 * h) : max(0, min(64, end - start - r0b)));  // wave-uniform
       if (nh > 0 && !psum) row_segment(r0b, nh);
       if (LQ_EVAL_OUT_AFTER_ROWS) lookup_out(h);
     }
@@ -1809,21 +1855,40 @@ struct EvalsArgs {
 #define LQ_EVALS_SKEW 0  // k_evals: start delay (100 MHz ticks) of the grid's second half (diagnostic builds)
 #endif
 
+// (k_evals' second argument in the kernel argument segment: after the first, at its own alignment)
+constexpr size_t KARG_X = (sizeof(EvalArgs) + alignof(EvalsArgs) - 1) / alignof(EvalsArgs) * alignof(EvalsArgs);
+static_assert(alignof(EvalArgs) <= 8 && alignof(EvalsArgs) <= 8, "k_evals reads its arguments at offsets 0 and KARG_X");
+
 template <int NT>
-__global__ __launch_bounds__(EVAL_EVS, EVAL_MIN_WAVES) void k_evals(EvalArgs a, EvalsArgs x) {
+__global__ __launch_bounds__(EVAL_EVS, EVAL_MIN_WAVES) void k_evals(EvalArgs a, EvalsArgs x_) {
   const int b = (int)blockIdx.x;
-  if (LQ_EVALS_SKEW > 0 && 2 * b >= x.nblk) {  // (the two workgroups of a CU out of phase)
+  if (LQ_EVALS_SKEW > 0 && 2 * b >= x_.nblk) {  // (the two workgroups of a CU out of phase)
     const long long t0 = __builtin_amdgcn_s_memrealtime();
     while (__builtin_amdgcn_s_memrealtime() - t0 < LQ_EVALS_SKEW) __builtin_amdgcn_s_sleep(8);
   }
-  for (int r = 0; r < x.nruns; ++r) {
+  for (int r = 0; r < x_.nruns; ++r) {
+#if LQ_EVALS_KARGS
+    // (the kernel's two argument structs read where they are used, from the argument segment through a
+    // pointer laundered per run: scalar loads that hit the scalar cache, instead of some 70 scalar registers
+    // held across the loop and spilled to vector lanes, each spill and reload a VALU instruction)
+    typedef __attribute__((address_space(4))) const EvalArgs karg_t;
+    typedef __attribute__((address_space(4))) const EvalsArgs kargx_t;
+    typedef __attribute__((address_space(4))) const char kargc_t;
+    karg_t* ka = (karg_t*)__builtin_amdgcn_kernarg_segment_ptr();
+    asm volatile("" : "+s"(ka));
+    const EvalArgs& ar = *(const EvalArgs*)ka;
+    const EvalsArgs& x = *(const EvalsArgs*)(kargx_t*)((kargc_t*)ka + KARG_X);
+#else
+    const EvalArgs& ar = a;
+    const EvalsArgs& x = x_;
+#endif
     const int j = x.run0 + r;
     RunOff ro;
     ro.tab = (int64_t)(j % x.slots) * x.SG;
     ro.rec = r * x.nblk;
     ro.ev = (int64_t)j * x.ev_stride;
-    ro.lmbd = a.lmbd + (size_t)j * x.lm_stride;
-    ro.lmbd_r = a.lmbd_r + (size_t)j * x.lr_stride;
+    ro.lmbd = ar.lmbd + (size_t)j * x.lm_stride;
+    ro.lmbd_r = ar.lmbd_r + (size_t)j * x.lr_stride;
     ro.launder = true;
     ro.gamma_lds = r > 0;
     ro.pipelined = LQ_EVALS_PIPELINED;
@@ -1840,7 +1905,7 @@ __global__ __launch_bounds__(EVAL_EVS, EVAL_MIN_WAVES) void k_evals(EvalArgs a, 
     // of its staging phases, the end of its rows and its end, at g_stamps[((b * 32 + r) * 8 + k]
     const long long t0__ = __builtin_amdgcn_s_memtime();
 #endif
-    eval_block<NT, false>(a, bl, nullptr, ro);
+    eval_block<NT, false>(ar, bl, nullptr, ro);
     // (no barrier here: every wave has passed the block's record barrier, so every row of the run is
     // written and its table no longer read; wave 0 reads only the row sums while the others stage the
     // next run, and no wave writes row sums again before the next run's staging barrier, which wave 0

@@ -1509,7 +1509,8 @@ __device__ __forceinline__ void eval_block(const EvalArgs& a, const int blk, con
   // row is a plain piece lookup (re-solved and invalid EVs read a zero piece), so the loop has
   // no per-row branch: the stores of a full batch use one address register and immediate
   // offsets; lanes past the row width (rlane false) store out of the descriptor's range, which
-  // drops them
+  // drops them (a w too large for a descriptor, B N 8 > LQ_DROP_OFF, takes plain stores: there those
+  // lanes' row is clamped to the segment, see the store)
   const bool fast = aw && a.w_rsrc_ok;
   const __amdgpu_buffer_rsrc_t rs =
       __builtin_amdgcn_make_buffer_rsrc(aw, (short)0, aw ? a.w_bytes : 0, 0x00020000);
@@ -1577,7 +1578,12 @@ __device__ __forceinline__ void eval_block(const EvalArgs& a, const int blk, con
               if (V == 2) st_wt16(rs, off, x0, x1);
               else st_wt8b(rs, off, x0);
             } else if (aw) {
-              double* dst = aw + (size_t)(rbase + r0 + j * R + rr) * N + t0;
+              // (the row the lane's key and gamma were read from: for the rows' lanes r0 + j R + rr itself;
+              // the lanes past the row width, which no descriptor drops here, hold row R of the instruction —
+              // the next row, a duplicate of its own store — clamped at the segment's end to its last row.
+              // Unclamped they wrote the last row's values into the next wave's first row or past the end
+              // of w)
+              double* dst = aw + (size_t)(rbase + min(r0 + j * R + rr, nrows - 1)) * N + t0;
               st_wt8(dst, x0);
               if (V == 2) st_wt8(dst + 1, x1);
             }

@@ -13,6 +13,11 @@
  *     a ``hipStream_t`` passed as ``void*`` (NULL = the legacy default stream).
  *   - "dev" pointers are device pointers owned by the caller (e.g. the
  *     data_ptr() of a PyTorch-ROCm tensor); "host" pointers are host memory.
+ *   - Alignment: every device pointer to doubles or int64 (gamma, lmbd, lmbd_r, w_ref, w, cost, w0,
+ *     set_sum_w, set_stats, ...) needs its natural 8-byte alignment and no more; int8 status needs none.
+ *     The w rows are written with 16-byte store instructions for even N, which do not require a 16-byte
+ *     aligned w (nor an even ev_stride N): measured with every pointer 8 bytes off a 16-byte boundary
+ *     (tests/test_gpu_extents.py), same results.
  *   - All device work is asynchronous on ``stream`` unless stated otherwise.
  *   - Counts are int64.  Every function returns an int status (LOMPC_OK = 0).
  *   - A context is bound to one device; it is not re-entrant (the reference's
@@ -106,7 +111,9 @@ int lompc_set_params(lompc_ctx* ctx, int64_t S, const double* lmbd,
  * which is one LoMPC.solve_lompc (lompc.py:137-156).
  *   gamma        dev  [B]      gamma_i = y_max - y0_i (price_solver.py:202)
  *   set_offsets  host [S+1]    EVs of set s are [set_offsets[s], set_offsets[s+1])
- *   w            dev  [B, N]   optimal w_i (row-major), or NULL
+ *   w            dev  [B, N]   optimal w_i (row-major), or NULL; 8-byte aligned (16 not required); B N 8
+ *                              bytes may exceed 2 GiB (rows past a buffer descriptor's range take plain
+ *                              stores: tests/test_gpu_extents.py)
  *   cost         dev  [B]      optimal cost incl. constant (lompc.py:155), or NULL
  *   w0           dev  [B]      w_i[0] (price_solver.py:282), or NULL
  *   status       dev  [B]      int8 LOMPC_QP_* per EV, or NULL

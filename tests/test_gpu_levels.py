@@ -2,10 +2,15 @@
 one descending sort per EV type gives the statistics the reference's index masks define
 (charging_station.py:111-116 with price_solver.py:66-77) and each partition's EVs as one run in
 descending charge level; levels exactly on boundaries, ties and an out-of-range level included."""
+import ctypes
+import math
+
 import numpy as np
 import pytest
 import torch
 
+from guarded import Guarded
+from lompc_amd import _lib
 from lompc_amd.charging_station import ChargingStation, partition_stats
 
 pytestmark = pytest.mark.gpu
@@ -140,3 +145,109 @@ def test_levels_stats_nan_fails_the_range_check(gpu, where):
     assert set(out) == {"Large"}
     rec = cs._lv["Small"]["stats"].cpu().numpy()
     assert np.isnan(rec[4 * P]) and np.isnan(rec[4 * P + 1])
+
+
+# ---------------------------------------------------------------------------------------------------
+# the three entry points called directly, on guarded buffers (tests/guarded.py), at the partition counts
+# and sizes where their code changes path: P = 13 .. 16 the top of k_lvh_partial's register arrays, 17 the
+# first count lompc_levels_stats refuses, 256 = LV_MAXP (the end of k_lv_gamma's LDS array); n below one
+# wave, around one wave and around the 4096-EV chunks of lompc_levels_stats' workgroups
+LV_P = [1, 2, 13, 16, 17, 256]
+LV_N = [1, 63, 64, 65, 4095, 4096, 4097, 40000]
+
+
+def _levels(kind, n, P, bounds, rs):
+    """spread: the lower 60 % of the range (the upper partitions empty), levels exactly on boundaries (the
+    outermost two included) and ties; one: every level in one middle partition, half of them tied."""
+    if kind == "one":
+        p = P // 2
+        y = bounds[p] + (bounds[p + 1] - bounds[p]) * (0.25 + 0.5 * rs.random(n))
+        y[::2] = y[0]
+        return y
+    y = bounds[0] + 0.6 * (bounds[P] - bounds[0]) * rs.random(n)
+    k = min(n, 24)
+    y[:k] = bounds[rs.integers(0, P + 1, k)]
+    if n >= 4:
+        y[n - 4:n - 2] = bounds[[0, P]]
+        y[n - 2:] = y[n // 2]
+    return y
+
+
+def _ref_stats(y, bounds):
+    P = len(bounds) - 1
+    idx = _ref_indices(y, bounds, np.zeros(len(y), dtype=np.int64))
+    ref = np.zeros((P, 4))
+    for p in range(P):
+        v = y[idx == p]
+        ref[p] = (len(v), v.max(), v.min(), math.fsum(v)) if len(v) else (0.0, -np.inf, np.inf, 0.0)
+    return idx, ref
+
+
+def _check_stats(st, y, bounds, ref):
+    P = len(bounds) - 1
+    np.testing.assert_array_equal(st[:4 * P].reshape(P, 4)[:, :3], ref[:, :3])
+    np.testing.assert_allclose(st[:4 * P].reshape(P, 4)[:, 3], ref[:, 3], rtol=1e-13)
+    np.testing.assert_array_equal(st[4 * P:], [y.max(), y.min(), bounds[0], bounds[P]])
+
+
+@pytest.mark.parametrize("n", LV_N)
+@pytest.mark.parametrize("P", LV_P)
+def test_levels_entry_points_extents(gpu, P, n):
+    """lompc_levels_layout, lompc_levels_stats and lompc_levels_gamma on guarded buffers: ys / perm bitwise
+    np.argsort(-y, kind="stable"), each partition's run the reference's index mask (later partitions
+    winning on shared edges), count / max / min exact, sums against math.fsum at 1e-13, the trailing four
+    statistics exact; work exactly *work_bytes long, gam exactly n + P central; lompc_levels_stats refuses
+    P > 16 with LOMPC_ERR_UNSUPPORTED and writes nothing; every band intact, every input unchanged."""
+    lib = _lib.load()
+    stream = torch.cuda.current_stream().cuda_stream
+    y_max = 0.9
+    bounds = np.linspace(0.3, y_max, P + 1)
+    for kind in ("spread", "one"):
+        rs = np.random.default_rng(1000 * P + n + (kind == "one"))
+        y = _levels(kind, n, P, bounds, rs)
+        idx, ref = _ref_stats(y, bounds)
+        order = np.argsort(-y, kind="stable")
+        counts = ref[::-1, 0].astype(np.int64)  # storage order: partition P - 1 first
+        runs = np.concatenate([[0], np.cumsum(counts)]).astype(np.int64)
+        gsc = y_max * rs.random(P)
+        wb_l, wb_s = ctypes.c_size_t(0), ctypes.c_size_t(0)
+        assert lib.lompc_levels_layout(None, n, None, P, None, None, None, None, ctypes.byref(wb_l), stream) == 0
+        rc_s = lib.lompc_levels_stats(None, n, None, P, None, None, ctypes.byref(wb_s), stream)
+        assert rc_s == (0 if P <= 16 else _lib.LOMPC_ERR_UNSUPPORTED) and wb_l.value > 0
+        gb = Guarded().inp("y", y).inp("bounds", bounds).inp("runs", runs).inp("gsc", gsc).inp("ys_in", y[order])
+        gb.out("ys", (n,)).out("perm", (n,), torch.int64).out("stats", (4 * P + 4,)).out("stats_h", (4 * P + 4,))
+        gb.out("gam0", (n,)).out("gam1", (n + P,))
+        gb.out("work_l", (wb_l.value,), torch.int8).out("work_s", (max(wb_s.value, 16),), torch.int8).build()
+        assert lib.lompc_levels_layout(gb.ptr("y"), n, gb.ptr("bounds"), P, gb.ptr("ys"), gb.ptr("perm"), gb.ptr("stats"),
+                                       gb.ptr("work_l"), ctypes.byref(wb_l), stream) == 0
+        rc = lib.lompc_levels_stats(gb.ptr("y"), n, gb.ptr("bounds"), P, gb.ptr("stats_h"), gb.ptr("work_s"), ctypes.byref(wb_s),
+                                    stream)
+        assert rc == rc_s
+        for central in (0, 1):
+            assert lib.lompc_levels_gamma(gb.ptr("ys_in"), n, gb.ptr("runs"), P, y_max, central, gb.ptr("gsc"),
+                                          gb.ptr(f"gam{central}"), stream) == 0
+        torch.cuda.synchronize()
+        gb.check_bands()
+        gb.check_inputs()
+        for name in ("ys", "perm", "stats", "gam0", "gam1"):
+            gb.check_written(name)
+        ys, perm = gb.np("ys"), gb.np("perm")
+        np.testing.assert_array_equal(perm, order)
+        assert np.array_equal(ys.view(np.int64), y[order].view(np.int64))
+        _check_stats(gb.np("stats"), y, bounds, ref)
+        for p in range(P):  # partition p: the run [c[p + 1], c[p]) of the descending levels
+            a, b = runs[P - 1 - p], runs[P - p]
+            assert np.array_equal(np.sort(perm[a:b]), np.nonzero(idx == p)[0]), p
+        if P <= 16:
+            gb.check_written("stats_h")
+            _check_stats(gb.np("stats_h"), y, bounds, ref)
+        else:
+            gb.check_untouched("stats_h")
+            gb.check_untouched("work_s")
+        g0, g1 = gb.np("gam0"), gb.np("gam1")
+        exp = y_max - y[order]
+        assert np.array_equal(g0.view(np.int64), exp.view(np.int64))
+        for k in range(P):
+            a, b = runs[k], runs[k + 1]
+            assert np.array_equal(g1[a + k:b + k].view(np.int64), exp[a:b].view(np.int64)), k
+            assert g1[b + k] == gsc[k], k

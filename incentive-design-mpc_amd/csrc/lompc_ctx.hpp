@@ -100,6 +100,7 @@ struct lompc_plan {
   int64_t B = 0, S = 0;
   int G = 0;                    // gamma cells per set (k_path waves per set)
   int cap = 0;                  // piece slots of one set the evaluation stages in LDS (eval_cap)
+  int scalar_cells = 0;         // LOMPC_PLAN_SCALAR_PASS: cells of one set k_scalar stages in LDS (scalar_cells_fit)
   int nblk = 0;                 // k_eval workgroups (blocks of one set's EVs)
   int n_cu = 0;
   bool close = false;           // the sets' closing inside k_eval (no k_finalize launch)
@@ -199,8 +200,8 @@ struct lompc_plan {
   int prof = 0;
   std::vector<hipEvent_t> prof_ev[LOMPC_PLAN_KERNELS], prof_pool;
   std::vector<int> prof_mult[LOMPC_PLAN_KERNELS];  // launches each recorded pair spans (1, or a span)
-  double prof_ms[LOMPC_PLAN_KERNELS] = {0.0, 0.0, 0.0};
-  int64_t prof_n[LOMPC_PLAN_KERNELS] = {0, 0, 0};
+  double prof_ms[LOMPC_PLAN_KERNELS] = {0.0, 0.0, 0.0, 0.0};
+  int64_t prof_n[LOMPC_PLAN_KERNELS] = {0, 0, 0, 0};
   std::string err;
 };
 
@@ -242,7 +243,8 @@ int lq_plan_prepare(lompc_plan* p, int nctx, lompc_ctx* const* ctxs, const int64
                     const double* gamma, const int64_t* set_offsets, const double* w_ref, int flags,
                     hipStream_t st);
 int lq_plan_launch(lompc_plan* p, const double* lmbd, const double* lmbd_r, double* w, double* cost, double* w0,
-                   int8_t* status, double* set_sum_w, double* set_stats, hipStream_t st, lompc_ctx* prof_ctx);
+                   int8_t* status, double* set_sum_w, double* set_stats, hipStream_t st, lompc_ctx* prof_ctx,
+                   bool scalar_ok = false);
 void lq_plan_free(lompc_plan* p);
 
 // RCCL communicator of the extension (lompc_comm.cpp; RCCL resolved at run time)

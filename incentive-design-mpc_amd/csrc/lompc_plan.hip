@@ -2065,6 +2065,7 @@ __global__ __launch_bounds__(256) void k_closes(FinalArgs f, ClosesArgs x) {
 }
 
 #include "lompc_agg.hpp"
+#include "lompc_scalar.hpp"
 
 // ---------------------------------------------------------------- k_loop_iter
 // One iteration of the device-resident price loop over gamma-sorted sets (lompc_loop.hip) in ONE
@@ -2664,6 +2665,46 @@ static int eval_cap(lompc_plan* p, int device, int N, int G, int* cap) {
   return LOMPC_OK;
 }
 
+// The cells of one set that k_scalar stages in LDS (LOMPC_PLAN_SCALAR_PASS): all G, lowered by whole cells
+// until scalar_lds fits beside the kernel's static LDS on the device (576 bytes per cell and 12 per cell
+// of the set: every G <= 256 fits whole at any horizon).  As for k_eval the request is checked here, on
+// the host: one past the limit is not refused at the launch, it aborts the queue.  The EVs of the cells
+// left unstaged take the certified individual re-solve.
+static int scalar_cells_fit(lompc_plan* p, int device, int G, int* cells) {
+  static std::mutex mu;
+  static std::map<int, size_t> known;
+  size_t room = 0;
+  {
+    std::lock_guard<std::mutex> lock(mu);
+    const auto it = known.find(device);
+    if (it != known.end()) {
+      room = it->second;
+    } else {
+      int limit = 0;
+      HIPCHK(p, hipDeviceGetAttribute(&limit, hipDeviceAttributeMaxSharedMemoryPerBlock, device));
+      hipFuncAttributes at;
+      HIPCHK(p, hipFuncGetAttributes(&at, (const void*)k_scalar));
+      room = (size_t)limit > (size_t)at.sharedSizeBytes ? (size_t)limit - (size_t)at.sharedSizeBytes : 0;
+      int occ = 0;  // (the runtime's own account must agree, as in eval_lds_room)
+      while (room >= 1024) {
+        HIPCHK(p, hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, (const void*)k_scalar, EVAL_EVS, room));
+        if (occ >= 1) break;
+        room -= 1024;
+      }
+      known[device] = room;
+    }
+  }
+  int c = G;
+  while (c > 1 && scalar_lds(G, c) > room) --c;
+  if (scalar_lds(G, c) > room) {
+    p->err = "plan: the scalar pass with " + std::to_string(G) + " cells per set does not fit a workgroup's LDS (" +
+             std::to_string(room) + " bytes)";
+    return LOMPC_ERR_UNSUPPORTED;
+  }
+  *cells = c;
+  return LOMPC_OK;
+}
+
 // events of one profiled dispatch (null events when kernel k is not profiled)
 int plan_prof_begin(lompc_plan* p, int k, hipEvent_t* e0, hipEvent_t* e1) {
   *e0 = *e1 = nullptr;
@@ -2731,6 +2772,9 @@ int lq_plan_prepare(lompc_plan* p, int nctx, lompc_ctx* const* ctxs, const int64
   LQ_PREP_MARK(1);
   int cap = 0;
   if (const int rc_cap = eval_cap(p, ctxs[0]->device, N, G, &cap)) return rc_cap;
+  int scalar_cells = 0;
+  if (flags & LOMPC_PLAN_SCALAR_PASS)
+    if (const int rc_sc = scalar_cells_fit(p, ctxs[0]->device, G, &scalar_cells)) return rc_sc;
   const int64_t occ_key = (int64_t)N * 4096 + cap;
   if (p->eval_occ_key != occ_key) {  // k_eval workgroups resident per CU (either variant may run)
     int occ0 = 0, occ1 = 0;
@@ -2810,6 +2854,7 @@ int lq_plan_prepare(lompc_plan* p, int nctx, lompc_ctx* const* ctxs, const int64
   p->S = S;
   p->G = G;
   p->cap = cap;
+  p->scalar_cells = scalar_cells;
   p->nblk = (int)nblk;
   p->n_empty = (int)n_empty;
   p->d_stats = p->d_stats_own;
@@ -3083,7 +3128,7 @@ int lq_exchange(lompc_plan* p, const double* send, double* set_sum_w, double* se
 
 int lq_launch_eval(lompc_plan* p, const double* lmbd, const double* lmbd_r, double* w, double* cost, double* w0,
                    int8_t* status, double* set_sum_w, double* set_stats, const PathTab& tb, hipStream_t st,
-                   lompc_ctx* prof_ctx, FinalArgs* defer = nullptr) {
+                   lompc_ctx* prof_ctx, FinalArgs* defer = nullptr, bool scalar_ok = false) {
   if (defer) defer->N = 0;
   const int N = p->N;
   EvalArgs a;
@@ -3100,8 +3145,13 @@ int lq_launch_eval(lompc_plan* p, const double* lmbd, const double* lmbd_r, doub
   r.set_stats = xr ? p->d_xsend + p->S * N : set_stats;
   // gamma-sorted sets and no per-EV output: per-piece aggregation (k_agg) instead of k_eval
   const bool agg = p->sorted && !w && !cost && !w0 && !status && p->nblk > 0;
-  const bool close = !agg && (p->close || (p->close_no_w && !w)) && p->nblk > 0;
   const bool cprof = prof_ctx && prof_ctx->prof;  // lompc_solve_batch: the context's k_eval timing
+  // the scalar pass (lompc_plan_run of a LOMPC_PLAN_SCALAR_PASS plan, the rule of lompc_amd.h): no w row and
+  // no per-stage sum asked for, so k_scalar evaluates from the coefficient records alone; k_finalize closes
+  const bool scalar = scalar_ok && (p->flags & LOMPC_PLAN_SCALAR_PASS) && !(p->flags & LOMPC_PLAN_DIAG_REPAIR) && !w &&
+                      !set_sum_w && (cost || w0 || status || set_stats) && !xr && !agg && !defer && !prof_ctx &&
+                      p->nblk > 0 && p->scalar_cells >= 1;
+  const bool close = !agg && !scalar && (p->close || (p->close_no_w && !w)) && p->nblk > 0;
   if (agg) {  // timed as k_eval
     hipEvent_t e0 = nullptr, e1 = nullptr;
     if (plan_prof_begin(p, LOMPC_PLAN_K_EVAL, &e0, &e1)) return fail_arg(p, "profiling events");
@@ -3112,6 +3162,13 @@ int lq_launch_eval(lompc_plan* p, const double* lmbd, const double* lmbd_r, doub
     hipExtLaunchKernelGGL(agg_kernel(N), dim3((unsigned)p->S), dim3(64 * nw), 0, st, e0, e1, 0, ga);
     HIPCHK(p, hipGetLastError());
     plan_prof_end(p, LOMPC_PLAN_K_EVAL, e0, e1);
+  } else if (scalar) {
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    if (plan_prof_begin(p, LOMPC_PLAN_K_SCALAR, &e0, &e1)) return fail_arg(p, "profiling events");
+    hipExtLaunchKernelGGL(k_scalar, dim3((unsigned)p->nblk), dim3(EVAL_EVS), scalar_lds(p->G, p->scalar_cells), st, e0, e1,
+                          0, a, p->scalar_cells);
+    HIPCHK(p, hipGetLastError());
+    plan_prof_end(p, LOMPC_PLAN_K_SCALAR, e0, e1);
   } else if (p->nblk > 0) {
     hipEvent_t e0 = nullptr, e1 = nullptr;
     if (cprof ? take_events(prof_ctx->prof_pool, &e0, &e1) : plan_prof_begin(p, LOMPC_PLAN_K_EVAL, &e0, &e1))
@@ -3146,11 +3203,12 @@ int lq_launch_eval(lompc_plan* p, const double* lmbd, const double* lmbd_r, doub
 }
 
 int lq_plan_launch(lompc_plan* p, const double* lmbd, const double* lmbd_r, double* w, double* cost, double* w0,
-                   int8_t* status, double* set_sum_w, double* set_stats, hipStream_t st, lompc_ctx* prof_ctx) {
+                   int8_t* status, double* set_sum_w, double* set_stats, hipStream_t st, lompc_ctx* prof_ctx,
+                   bool scalar_ok) {
   const PathTab tb = own_tab(p);
   int rc = lq_launch_path(p, lmbd, lmbd_r, tb, st);
   if (rc) return rc;
-  return lq_launch_eval(p, lmbd, lmbd_r, w, cost, w0, status, set_sum_w, set_stats, tb, st, prof_ctx);
+  return lq_launch_eval(p, lmbd, lmbd_r, w, cost, w0, status, set_sum_w, set_stats, tb, st, prof_ctx, nullptr, scalar_ok);
 }
 
 bool lq_loop_fusable(const lompc_plan* p, bool persistent) {  // (S = 2: the loop's sets; ctl holds 2 set counters)
@@ -3888,7 +3946,8 @@ int lompc_plan_run(lompc_plan* p, const double* lmbd, const double* lmbd_r, doub
                    int8_t* status, double* set_sum_w, double* set_stats, void* stream) {
   if (!p) return LOMPC_ERR_INVALID_ARG;
   HIPCHK(p, hipSetDevice(p->device));
-  return lq_plan_launch(p, lmbd, lmbd_r, w, cost, w0, status, set_sum_w, set_stats, (hipStream_t)stream, nullptr);
+  // (the one entry point that may take the scalar pass of a LOMPC_PLAN_SCALAR_PASS plan)
+  return lq_plan_launch(p, lmbd, lmbd_r, w, cost, w0, status, set_sum_w, set_stats, (hipStream_t)stream, nullptr, true);
 }
 
 int lompc_plan_run_steps(lompc_plan* p, const double* lmbd, int64_t lmbd_stride, const double* lmbd_r,

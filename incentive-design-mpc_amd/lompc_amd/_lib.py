@@ -32,12 +32,14 @@ LOMPC_PLAN_MAX_CTX = 4
 LOMPC_PLAN_K_PATH = 0
 LOMPC_PLAN_K_EVAL = 1
 LOMPC_PLAN_K_FINAL = 2
-LOMPC_PLAN_KERNELS = 3
+LOMPC_PLAN_K_SCALAR = 3
+LOMPC_PLAN_KERNELS = 4
 LOMPC_PLAN_WARM_START = 1
 LOMPC_PLAN_DIAG_REPAIR = 2
 LOMPC_PLAN_CLOSE_IN_EVAL = 8
 LOMPC_PLAN_SORTED_GAMMA = 16
 LOMPC_PLAN_CLOSE_IN_FINALIZE = 32
+LOMPC_PLAN_SCALAR_PASS = 64
 LOMPC_PLAN_CELLS_SHIFT = 20
 LOMPC_STEPS_PER_KERNEL = 1
 LOMPC_STEPS_SPAN_EVENTS = 2

@@ -182,6 +182,9 @@ class ChargingStation:
         self._gl_host, self._gl_keep = {}, {}  # _gamma_layout's pinned run bounds per price solver
         # the w0 / price0 pass of both types in one engine run (False: one per type — A/B timing)
         self.w0_one_call = True
+        # _w0_both's plan takes the engine's scalar pass (BatchPlan scalar_pass: k_scalar, per-EV w0 bit for
+        # bit, the partition sums to rounding); read when that plan is created.  Default: see DESIGN.md §9
+        self.w0_scalar_pass = True
         self._w0plan, self._w0_host, self._w0_keep = None, None, None
         self.device = torch.cuda.current_device() if device is None else int(device)
         self._dev = f"cuda:{self.device}"
@@ -922,7 +925,7 @@ class ChargingStation:
         if plan is None:
             plan = self._w0plan = BatchPlan([self.price_solver_s.lompc, self.price_solver_l.lompc], gamma, off,
                                             sets_per_ctx=[P, P], want_w=False, want_cost=False, want_w0=True,
-                                            want_set=True, validate=False)
+                                            want_set=True, validate=False, scalar_pass=self.w0_scalar_pass)
         else:
             plan.update(gamma, off, validate=False)
         hb = self._w0_host

@@ -350,13 +350,22 @@ class BatchPlan:
     their sets in the k_finalize launch as well (A/B of the close mode).  ``cells``: gamma cells per
     set instead of the plan's choice (the answer does not depend on it).  ``set_comm(comm)``: a
     sharded batch — every run combines the set reductions of all ranks on the device (RCCL).
+    ``scalar_pass`` (LOMPC_PLAN_SCALAR_PASS; not with want_w or sort_sets): the contract of
+    PriceSolver.get_w0_price0 (price_solver.py:272-285) — ``run`` evaluates every EV from its piece's
+    64-byte coefficient record alone (k_scalar; no piece rows staged, no per-stage sums built) and the
+    sets close in k_finalize.  With want_set the plan allocates and passes ``set_stats`` only: ``run``
+    returns no ``set_sum_w``.  Per-EV cost / w0 / status are bit-identical to the default evaluation's;
+    the set sums (SUM_W0, SUM_PRICE0, SUM_COST) equal it to rounding (another fixed summation order) and
+    are the same bits in every run.  The pass is taken by ``run`` only, without a communicator and
+    without diag_repair; a sorted_gamma plan with no per-EV output keeps its aggregation; ``run_steps``
+    and ``run_chain`` evaluate as an unflagged plan does.  ``update`` keeps the flag.
     DIRECT-mode contexts fall back to ``lompc_run`` (one context only).
     """
 
     def __init__(self, lompc, gamma, set_offsets, *, sets_per_ctx=None, w_ref=None, gamma_ref=None, want_w=True,
                  want_cost=True, want_w0=False, want_status=False, want_set=True, stream=None, validate=True,
                  warm_start=False, diag_repair=False, close_in_eval=False, sorted_gamma=False,
-                 close_in_finalize=False, cells=None, sort_sets=False):
+                 close_in_finalize=False, cells=None, sort_sets=False, scalar_pass=False):
         torch = _torch()
         lompcs = list(lompc) if isinstance(lompc, (list, tuple)) else [lompc]
         self.lompcs = lompcs
@@ -380,6 +389,11 @@ class BatchPlan:
         self.sort_sets = bool(sort_sets)
         if self.sort_sets and (want_w or want_cost or want_w0 or want_status):
             raise ValueError("sort_sets: plans without per-EV outputs only (the EVs are reordered)")
+        self.scalar_pass = bool(scalar_pass)
+        if self.scalar_pass and want_w:
+            raise ValueError("scalar_pass: plans without w rows only (want_w=False)")
+        if self.scalar_pass and self.sort_sets:
+            raise ValueError("scalar_pass: per-EV outputs in the caller's order, not with sort_sets")
         sorted_gamma = sorted_gamma or self.sort_sets
         self._stream = (stream if stream is not None else torch.cuda.current_stream(lo.device)).cuda_stream
         self._lib = lo._lib
@@ -399,6 +413,7 @@ class BatchPlan:
                  | (_lib.LOMPC_PLAN_CLOSE_IN_EVAL if close_in_eval else 0)
                  | (_lib.LOMPC_PLAN_SORTED_GAMMA if sorted_gamma else 0)
                  | (_lib.LOMPC_PLAN_CLOSE_IN_FINALIZE if close_in_finalize else 0)
+                 | (_lib.LOMPC_PLAN_SCALAR_PASS if self.scalar_pass else 0)
                  | (_lib.LOMPC_PLAN_CELLS(cells) if cells else 0))
         self._flags = flags
         rc = self._lib.lompc_plan_create(len(lompcs), ctypes.cast(ctxs, ctypes.c_void_p), self.sets_per_ctx.ctypes.data,
@@ -452,7 +467,7 @@ class BatchPlan:
                 "cost": e((B,)) if wt["cost"] else None,
                 "w0": e((B,)) if wt["w0"] else None,
                 "status": e((B,), torch.int8) if wt["status"] else None,
-                "set_sum_w": e((S, N)) if wt["set"] else None,
+                "set_sum_w": e((S, N)) if wt["set"] and not getattr(self, "scalar_pass", False) else None,
                 "set_stats": e((S, _lib.LOMPC_SET_STATS)) if wt["set"] else None,
             }
             self._outs = [_ptr(self.out[k]) for k in ("w", "cost", "w0", "status", "set_sum_w", "set_stats")]
@@ -469,6 +484,9 @@ class BatchPlan:
             return 2
         if self._flags & _lib.LOMPC_PLAN_SORTED_GAMMA and not any(self._want[k] for k in ("w", "cost", "w0", "status")):
             return 2 + (2 if self.comm is not None else 0)  # k_path + k_agg
+        if self.scalar_pass and self.comm is None and self.B > 0 and not self._flags & _lib.LOMPC_PLAN_DIAG_REPAIR \
+                and any(self._want[k] for k in ("cost", "w0", "status", "set")):
+            return 3  # k_path + k_scalar + k_finalize
         close = bool(self._flags & _lib.LOMPC_PLAN_CLOSE_IN_EVAL) or (
             not self._want["w"] and not self._flags & _lib.LOMPC_PLAN_CLOSE_IN_FINALIZE)
         return (2 if close else 3) + (2 if self.comm is not None else 0)
@@ -690,22 +708,23 @@ class BatchPlan:
         return rep.value, fail.value, inv.value
 
     KERNELS = ("k_path", "k_eval", "k_finalize")
+    ALL_KERNELS = KERNELS + ("k_scalar",)  # (LOMPC_PLAN_K_*; k_scalar: the scalar pass's evaluation)
 
     def profile(self, enable=None, read: bool = False, reset: bool = False, kernel: str = "k_eval"):
         """HIP-event timing of the plan's kernels (DIRECT: k_direct only).
 
-        enable: True (k_eval), False, or a collection of kernel names from KERNELS;
+        enable: True (k_eval), False, or a collection of kernel names from ALL_KERNELS;
         read: (total ms, launches) of ``kernel`` since the last reset."""
         if self.direct:
             return self.lompc.profile(enable=enable, read=read, reset=reset)
         if enable is not None:
             if enable is True:
                 enable = ("k_eval",)
-            mask = 0 if enable is False else sum(1 << self.KERNELS.index(k) for k in enable)
+            mask = 0 if enable is False else sum(1 << self.ALL_KERNELS.index(k) for k in enable)
             self._check_rc(self._lib.lompc_plan_profile_enable(self._plan, mask))
         if read:
             ms, n = ctypes.c_double(0.0), ctypes.c_int64(0)
-            self._check_rc(self._lib.lompc_plan_profile_read(self._plan, self.KERNELS.index(kernel), ctypes.byref(ms),
+            self._check_rc(self._lib.lompc_plan_profile_read(self._plan, self.ALL_KERNELS.index(kernel), ctypes.byref(ms),
                                                              ctypes.byref(n), int(bool(reset))))
             return ms.value, n.value
         return None

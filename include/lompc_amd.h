@@ -196,6 +196,27 @@ typedef struct lompc_plan lompc_plan;
 #define LOMPC_PLAN_CLOSE_IN_FINALIZE 32 /* runs without w output close their sets in the k_finalize
                                            launch like runs with w (default: inside k_eval); the
                                            A/B form of the close-mode parity tests */
+#define LOMPC_PLAN_SCALAR_PASS 64 /* the scalar pass: a lompc_plan_run that asks for no w row and no per-stage
+                                     sum evaluates its EVs from the path table's 64-byte coefficient records
+                                     alone (k_scalar: no piece rows staged, 72 bytes of LDS per piece slot
+                                     instead of 16 N + 72) — the call shape of PriceSolver.get_w0_price0
+                                     (price_solver.py:272-285).  lompc_plan_run takes it exactly when ALL hold:
+                                     the plan has this flag; w == NULL and set_sum_w == NULL; at least one of
+                                     cost, w0, status, set_stats is non-NULL; no communicator is attached; the
+                                     plan has at least one EV; LOMPC_PLAN_DIAG_REPAIR is off; and the run is
+                                     not the aggregation of a LOMPC_PLAN_SORTED_GAMMA plan with no per-EV output
+                                     (those stay O(pieces)).  In every other case, and in every other entry
+                                     point (lompc_plan_run_steps, lompc_plan_run_chain, lompc_price_loop,
+                                     lompc_solve_batch, lompc_run), a flagged plan behaves exactly as an
+                                     unflagged one.  Contract: per-EV cost, w0 and status carry the same bits
+                                     as the default evaluation's (the same lookup and fma forms; EVs no staged
+                                     piece covers take the same certified re-solve); the set_stats sums
+                                     (SUM_W0, SUM_PRICE0, SUM_COST) are summed in another fixed order, so they
+                                     equal the default's to rounding, and are the same bits in every run on the
+                                     same inputs; counts and MAX_ERR as the default.  The sets close in the
+                                     k_finalize launch whatever the plan's CLOSE_IN_* flags say.  The pass
+                                     stages every cell of a set up to 256 (more: as many as the device's LDS
+                                     holds; the EVs of the others are re-solved one by one, exact but slow). */
 /* gamma cells per set (1 .. 1024, at every horizon; more: LOMPC_ERR_INVALID_ARG at create) instead of
  * the plan's own choice: flags | LOMPC_PLAN_CELLS(g).  The answer does not depend on it (every piece
  * is certified); it trades per-cell tracking latency against cold starts.  The
@@ -346,7 +367,9 @@ int lompc_plan_get_info(const lompc_plan* plan, int64_t* B, int64_t* S, int* cel
 #define LOMPC_PLAN_K_PATH 0  /* per-(set, gamma cell) solution paths */
 #define LOMPC_PLAN_K_EVAL 1  /* per-EV evaluation (the HBM-bound kernel) */
 #define LOMPC_PLAN_K_FINAL 2 /* per-set reduction + individual re-solves */
-#define LOMPC_PLAN_KERNELS 3
+#define LOMPC_PLAN_K_SCALAR 3 /* the scalar pass's per-EV evaluation (LOMPC_PLAN_SCALAR_PASS; such a run
+                                 records no LOMPC_PLAN_K_EVAL launch) */
+#define LOMPC_PLAN_KERNELS 4
 int lompc_plan_profile_enable(lompc_plan* plan, int kernel_mask);
 int lompc_plan_profile_read(lompc_plan* plan, int kernel, double* total_ms, int64_t* launches, int reset);
 

@@ -304,7 +304,14 @@ class PriceSolver:
             B = int(gamma.numel())
             gamma = gamma.reshape(-1).to(dtype=torch.float64).contiguous()
             self._gam = torch.empty(B + central, dtype=torch.float64, device=self._dev)
-            self._gam[:B] = gamma if presorted else torch.sort(gamma).values
+            if presorted:
+                self._gam[:B] = gamma
+            else:
+                # a sorted set holds its valid gamma first and the invalid ones (NaN, outside [0, y_max])
+                # behind them.  A level above y_max gives gamma < 0, which a plain sort puts in FRONT: the
+                # set would read as unsorted (SolverError) instead of as holding an invalid level
+                # (AssertionError, price_solver.py:71).  As +inf it sorts behind the values, before the NaN.
+                self._gam[:B] = torch.sort(torch.where(gamma < 0, torch.inf, gamma)).values
             self._gam_w0 = gamma
             self._gcentral = None if not central else self._gam[B:]
             if central:

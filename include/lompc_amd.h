@@ -433,6 +433,17 @@ int lompc_combine_records(const double* recv, int nranks, int64_t S, int N, doub
  * depends only on the iteration count, so sharded ranks issue the same collectives.  Requires
  * A_bar = A'A + kappa I (as PriceSolver passes; otherwise the host loop runs).
  * device_loop = 0: the host loop above (one D2H copy + stream sync per iteration).
+ * Ends other than convergence, the same in every form: the cap (above); LOMPC_ERR_INVALID_ARG for a
+ * gamma outside [0, y_max] in either set (tested after every engine call; the plan's error text names
+ * gamma); LOMPC_ERR_NOT_CONVERGED for EVs without a certified optimum, for an unsorted set of a
+ * LOMPC_PLAN_SORTED_GAMMA plan (the text says so) and for a price QP without a certificate.  On an
+ * error no output is written.  max_iter < 1, n_evs <= 0, r outside {2N, 3N} and a plan whose S is not
+ * 2 or whose horizon is not N are refused (LOMPC_ERR_INVALID_ARG) before anything is launched.
+ * After ANY of these ends the plan is ready for its next loop, which computes bit for bit what it
+ * computes on a fresh plan: a loop leaves behind only the plan's warm working sets (they change no
+ * result bit) and the plan's sticky tallies, which count every engine call that ran — those of a
+ * capped or failed loop included — until lompc_plan_status reads them.  Engine calls enqueued past
+ * the end run nothing and tally nothing.
  * prof (may be NULL): accumulates the loop's time per part, [LOMPC_LOOP_PROF] entries: */
 #define LOMPC_LOOP_PROF_ITERS  0 /* engine calls (plan runs)                                     */
 #define LOMPC_LOOP_PROF_WALL   1 /* us, host wall time of the whole loop                          */

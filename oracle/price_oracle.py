@@ -127,6 +127,9 @@ class OraclePriceSolver:
         # (fast along a price loop, whose iterations move the prices a little)
         self.warm = False
         self._ws = {}
+        # settings.py PRICE_SOLVER_TOL_TYPE: "avg" tests the average error, "max" the largest per-EV error
+        # (price_solver.py:379-383)
+        self.tol_type = "avg"
 
     def set_charge_levels(self, y0):
         self.nEVs, self.y0_rng, self.gamma_sc, self.gamma_sm = O.set_charge_levels(y0, self.consts.y_max)
@@ -168,8 +171,11 @@ class OraclePriceSolver:
         w_k, dual_cost = self.lompc.solve_lompc(lmbd_k, lmbd_r, self.gamma_sc)
         ac, pred = [], []
         for it in range(MAX_ITERS):
-            _, _, w_avg_err = self._get_w_err(lmbd_k, lmbd_r, w_ref, A_bar, want_max=False)
-            if w_avg_err <= tol:
+            if self.tol_type == "max":
+                w_err, _, _ = self._get_w_err(lmbd_k, lmbd_r, w_ref, A_bar, want_max=True)
+            else:
+                _, _, w_err = self._get_w_err(lmbd_k, lmbd_r, w_ref, A_bar, want_max=False)
+            if w_err <= tol:
                 break
             lmbd_k_new[:r], dec = price_step(N, r, th, wm, self.m, A_bar_inv, w_ref, w_k, lmbd_k[:r])
             w_k, dual_cost_new = self.lompc.solve_lompc(lmbd_k_new, lmbd_r, self.gamma_sc)

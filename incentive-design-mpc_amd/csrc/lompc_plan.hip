@@ -2665,8 +2665,8 @@ static int eval_cap(lompc_plan* p, int device, int N, int G, int* cap) {
   return LOMPC_OK;
 }
 
-// The cells of one set that k_scalar stages in LDS (LOMPC_PLAN_SCALAR_PASS): all G, lowered by whole cells
-// until scalar_lds fits beside the kernel's static LDS on the device (576 bytes per cell and 12 per cell
+// The cells of one set that k_scalar / k_scalars stage in LDS (LOMPC_PLAN_SCALAR_PASS): all G, lowered by whole cells
+// until scalar_lds fits beside the kernels' static LDS on the device (576 bytes per cell and 12 per cell
 // of the set: every G <= 256 fits whole at any horizon).  As for k_eval the request is checked here, on
 // the host: one past the limit is not refused at the launch, it aborts the queue.  The EVs of the cells
 // left unstaged take the certified individual re-solve.
@@ -2682,14 +2682,22 @@ static int scalar_cells_fit(lompc_plan* p, int device, int G, int* cells) {
     } else {
       int limit = 0;
       HIPCHK(p, hipDeviceGetAttribute(&limit, hipDeviceAttributeMaxSharedMemoryPerBlock, device));
-      hipFuncAttributes at;
-      HIPCHK(p, hipFuncGetAttributes(&at, (const void*)k_scalar));
-      room = (size_t)limit > (size_t)at.sharedSizeBytes ? (size_t)limit - (size_t)at.sharedSizeBytes : 0;
-      int occ = 0;  // (the runtime's own account must agree, as in eval_lds_room)
-      while (room >= 1024) {
-        HIPCHK(p, hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, (const void*)k_scalar, EVAL_EVS, room));
-        if (occ >= 1) break;
-        room -= 1024;
+      // (k_scalar and k_scalars: either may run the plan, so the larger static LDS counts)
+      const void* const kern[2] = {(const void*)k_scalar, (const void*)k_scalars};
+      size_t fixed = 0;
+      for (const void* f : kern) {
+        hipFuncAttributes at;
+        HIPCHK(p, hipFuncGetAttributes(&at, f));
+        fixed = std::max(fixed, (size_t)at.sharedSizeBytes);
+      }
+      room = (size_t)limit > fixed ? (size_t)limit - fixed : 0;
+      for (const void* f : kern) {  // (the runtime's own account must agree, as in eval_lds_room)
+        int occ = 0;
+        while (room >= 1024) {
+          HIPCHK(p, hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, f, EVAL_EVS, room));
+          if (occ >= 1) break;
+          room -= 1024;
+        }
       }
       known[device] = room;
     }
@@ -3643,7 +3651,7 @@ int wide_ring(lompc_plan* p, hipStream_t st) {
 int lq_run_steps_stepped(lompc_plan* p, const double* lmbd, int64_t lmbd_stride, const double* lmbd_r,
                          int64_t lmbd_r_stride, int n_runs, int profile_every, bool span_events, double* w, double* cost,
                          double* w0, int8_t* status, int64_t ev_stride, double* set_sum_w, int64_t sw_stride,
-                         double* set_stats, int64_t st_stride, bool split, hipStream_t st) {
+                         double* set_stats, int64_t st_stride, bool split, hipStream_t st, bool scalar = false) {
   auto& z = p->stp;
   int rc;
   const int N = p->N;
@@ -3707,6 +3715,8 @@ int lq_run_steps_stepped(lompc_plan* p, const double* lmbd, int64_t lmbd_stride,
     // batched: per path group of n <= Kc runs THREE launches — k_paths (the n paths), k_evals (the n
     // evaluations, each workgroup through its block of every run) and k_closes (the n x S closings);
     // the same kernels' arithmetic as the split form below, so the same bits
+    // (scalar — LOMPC_STEPS_SCALAR_PASS, the rule of lompc_amd.h: k_scalars instead of k_evals, one workgroup
+    // per (run, block) on the same block map and record slots, timed as K_SCALAR)
     // record slots x blocks, bounded like the table ring: a run's slot holds every block's record, its
     // re-solve counts and its re-solve list (EVAL_MAXB indices per block), so a batch of many blocks
     // takes smaller groups instead of gigabytes of mostly empty lists (the runs are independent: the
@@ -3754,17 +3764,22 @@ int lq_run_steps_stepped(lompc_plan* p, const double* lmbd, int64_t lmbd_stride,
         hipExtLaunchKernelGGL(paths_kernel(N), dim3((unsigned)(n * ncell)), dim3(64), 0, st, e0, e1, 0, pw, lmbd_stride,
                               lmbd_r_stride, g0, slots);
         HIPCHK(p, hipGetLastError());
-        plan_prof_end(p, LOMPC_PLAN_K_PATH, e0, e1);
+        plan_prof_end(p, LOMPC_PLAN_K_PATH, e0, e1, scalar ? n : 1);  // (scalar: every launch of the form read as its runs)
       }
-      {  // the evaluation launch carries the K_EVAL timing (span: the first group's only), as n runs
+      {  // the evaluation launch carries the K_EVAL (scalar: K_SCALAR) timing (span: the first group's only), as n runs
         hipEvent_t e0 = nullptr, e1 = nullptr;
         const bool ev = !span_events || g0 == 0;
-        if (ev && plan_prof_begin(p, LOMPC_PLAN_K_EVAL, &e0, &e1)) return fail_arg(p, "profiling events");
+        const int kk = scalar ? LOMPC_PLAN_K_SCALAR : LOMPC_PLAN_K_EVAL;
+        if (ev && plan_prof_begin(p, kk, &e0, &e1)) return fail_arg(p, "profiling events");
         const EvalsArgs x{g0, n, slots, z.nblk, lmbd_stride, lmbd_r_stride, ev_stride, ncell};
-        hipExtLaunchKernelGGL(z.stg ? evals_st_kernel(N) : evals_kernel(N), dim3((unsigned)z.nblk), dim3(EVAL_EVS), lds_e, st,
-                              e0, e1, 0, ea, x);
+        if (scalar)
+          hipExtLaunchKernelGGL(k_scalars, dim3((unsigned)(n * z.nblk)), dim3(EVAL_EVS), scalar_lds(p->G, p->scalar_cells), st,
+                                e0, e1, 0, ea, x, p->scalar_cells, K - 1);
+        else
+          hipExtLaunchKernelGGL(z.stg ? evals_st_kernel(N) : evals_kernel(N), dim3((unsigned)z.nblk), dim3(EVAL_EVS), lds_e, st,
+                                e0, e1, 0, ea, x);
         HIPCHK(p, hipGetLastError());
-        if (ev) plan_prof_end(p, LOMPC_PLAN_K_EVAL, e0, e1, n);
+        if (ev) plan_prof_end(p, kk, e0, e1, n);
       }
       {
         hipEvent_t e0 = nullptr, e1 = nullptr;
@@ -3946,7 +3961,7 @@ int lompc_plan_run(lompc_plan* p, const double* lmbd, const double* lmbd_r, doub
                    int8_t* status, double* set_sum_w, double* set_stats, void* stream) {
   if (!p) return LOMPC_ERR_INVALID_ARG;
   HIPCHK(p, hipSetDevice(p->device));
-  // (the one entry point that may take the scalar pass of a LOMPC_PLAN_SCALAR_PASS plan)
+  // (takes the scalar pass of a LOMPC_PLAN_SCALAR_PASS plan; lompc_plan_run_steps only on request: LOMPC_STEPS_SCALAR_PASS)
   return lq_plan_launch(p, lmbd, lmbd_r, w, cost, w0, status, set_sum_w, set_stats, (hipStream_t)stream, nullptr, true);
 }
 
@@ -3954,11 +3969,13 @@ int lompc_plan_run_steps(lompc_plan* p, const double* lmbd, int64_t lmbd_stride,
                          int64_t lmbd_r_stride, int n_runs, int profile_every, double* w, double* cost, double* w0,
                          int8_t* status, double* set_sum_w, double* set_stats, int64_t set_sum_w_stride,
                          int64_t set_stats_stride, int64_t ev_stride, int steps_flags, void* stream) {
-  constexpr int known = LOMPC_STEPS_PER_KERNEL | LOMPC_STEPS_SPAN_EVENTS;
+  constexpr int known = LOMPC_STEPS_PER_KERNEL | LOMPC_STEPS_SPAN_EVENTS | LOMPC_STEPS_SCALAR_PASS;
   if (!p || n_runs < 0 || profile_every < 0 || set_sum_w_stride < 0 || set_stats_stride < 0 || ev_stride < 0 ||
       (steps_flags & ~known))
     return LOMPC_ERR_INVALID_ARG;
   if (ev_stride > 0 && ev_stride < p->B) return fail_arg(p, "run_steps: 0 or ev_stride >= B required");
+  if ((steps_flags & LOMPC_STEPS_SCALAR_PASS) && !(p->flags & LOMPC_PLAN_SCALAR_PASS))
+    return fail_arg(p, "run_steps: LOMPC_STEPS_SCALAR_PASS requires a plan created with LOMPC_PLAN_SCALAR_PASS");
   HIPCHK(p, hipSetDevice(p->device));
   hipStream_t st = (hipStream_t)stream;
   // stepped form: the k_eval / k_finalize plans (not k_agg, not closed inside k_eval on request),
@@ -3966,6 +3983,17 @@ int lompc_plan_run_steps(lompc_plan* p, const double* lmbd, int64_t lmbd_stride,
   // sums the rows it does not store)
   const bool per_ev = w || cost || w0 || status;
   const bool agg = p->sorted && !per_ev;
+  // the wide scalar form (LOMPC_STEPS_SCALAR_PASS on a LOMPC_PLAN_SCALAR_PASS plan, the rule of lompc_amd.h): the
+  // wide form's three launches per group with k_scalars as the evaluation.  A per-call condition that fails
+  // leaves the call exactly as without the flag.
+  const bool scalar = (steps_flags & LOMPC_STEPS_SCALAR_PASS) && !(p->flags & (LOMPC_PLAN_DIAG_REPAIR | LOMPC_PLAN_WARM_START)) &&
+                      wide_fit(p) >= 1 && !w && !set_sum_w && (per_ev || set_stats) && !p->comm && !agg && !p->skip &&
+                      n_runs >= 1 && p->nblk > 0 && p->scalar_cells >= 1;
+  if (scalar)
+    return lq_run_steps_stepped(p, lmbd, lmbd_stride, lmbd_r, lmbd_r_stride, n_runs, profile_every,
+                                (steps_flags & LOMPC_STEPS_SPAN_EVENTS) != 0, nullptr, cost, w0, status, ev_stride, nullptr,
+                                set_sum_w_stride, set_stats, set_stats_stride,
+                                (steps_flags & LOMPC_STEPS_PER_KERNEL) != 0, st, true);
   // gamma-sorted sets without per-EV output: per group of runs one k_paths and one k_aggs launch
   // (the sequential form below on request: LOMPC_STEPS_PER_KERNEL, the same bits)
   if (n_runs >= 1 && !p->skip && agg && p->nblk > 0 && (p->flags & LOMPC_PLAN_WARM_START) == 0 &&

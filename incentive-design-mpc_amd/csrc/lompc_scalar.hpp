@@ -13,6 +13,9 @@
 // columns 1 .. N - 1 zero; fail_cnt[nblk][EVAL_WAVES]; fail_idx[nblk][EVAL_MAXB], 64 EVAL_PASSES per
 // wave — so the unchanged k_finalize closes the run: records summed in its fixed order, the listed
 // EVs re-solved individually, the sticky tallies kept.
+//
+// k_scalars (below) is the same pass for the runs of a wide-form group (lompc_plan_run_steps with
+// LOMPC_STEPS_SCALAR_PASS): both kernels call scalar_block, so the arithmetic exists once.
 #pragma once
 
 // waves per SIMD the compiler must fit (<= 64 VGPRs): four 8-wave workgroups per CU, which the
@@ -27,15 +30,22 @@ __host__ __device__ inline size_t scalar_lds(int G, int gs) {
   return (size_t)gs * LQ_PPL * 9 * sizeof(double) + (size_t)G * sizeof(double) + (size_t)((G + 1) & ~1) * sizeof(int);
 }
 
-__global__ __launch_bounds__(EVAL_EVS, LQ_SCALAR_MIN_WAVES) void k_scalar(EvalArgs a, int gs) {
+// One block of one run: k_scalar's whole body, shared with k_scalars.  ro: where the run's tables
+// (ro.tab, cells), its records (ro.rec, blocks), its per-EV outputs (ro.ev, EVs) and its prices sit, as
+// k_evals hands them to eval_block (k_scalar: all zero / the arguments' own).  store: the per-EV outputs
+// are written (k_scalars with one shared per-EV buffer: by the call's last run only).
+__device__ __forceinline__ void scalar_block(const EvalArgs& a, const int gs, const int blk, const RunOff ro,
+                                             const bool store) {
   // dynamic LDS: [np][8] coefficient records (cfx) | [LQ_PPL][Gs] piece ends (transposed, as k_eval) |
   // [G] coverage starts | [G] piece counts
   extern __shared__ __attribute__((aligned(16))) double2 s_dyn[];
   __shared__ double s_red[EVAL_WAVES][8];  // wave records: the NPX scalars, [7] = the wave's sum of w0
-  if (a.skip && *a.skip) return;
   const int tid = (int)threadIdx.x, lane = tid & 63, wv = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int blk = (int)blockIdx.x;
   const int4 info = a.blk[blk];
+  const size_t rb = (size_t)ro.rec + blk;  // this block's record (k_scalars: in its run's record slot)
+  double* const acost = store && a.cost ? a.cost + ro.ev : nullptr;
+  double* const aw0 = store && a.w0 ? a.w0 + ro.ev : nullptr;
+  int8_t* const astatus = store && a.status ? a.status + ro.ev : nullptr;
   const int s = info.x, start = info.y, end = info.z;  // thread: EVs start + tid + EVAL_EVS h
   const int N = a.N, G = a.G, Gs = gs;
   const int np = Gs * LQ_PPL;  // staged piece slots: the set's first Gs cells (the rest are re-solved)
@@ -53,10 +63,10 @@ __global__ __launch_bounds__(EVAL_EVS, LQ_SCALAR_MIN_WAVES) void k_scalar(EvalAr
   // the set's scalars (wave-uniform: scalar loads)
   const QPConst& q = set_consts(a.qd, a.ce, s);
   const double wlo = a.window[2 * s], whi = a.window[2 * s + 1];
-  const double* __restrict__ L = a.lmbd + (size_t)s * 3 * N;
+  const double* __restrict__ L = (ro.lmbd ? ro.lmbd : a.lmbd) + (size_t)s * 3 * N;
   const double l0[3] = {L[0], L[N], L[2 * N]};  // price0 (lompc.py:164-170)
-  const double lr = a.lmbd_r[s];
-  const int64_t cb = (int64_t)s * G;  // the set's first cell in the table
+  const double lr = (ro.lmbd_r ? ro.lmbd_r : a.lmbd_r)[s];
+  const int64_t cb = ro.tab + (int64_t)s * G;  // the set's first cell in the table
   const size_t sb = (size_t)cb * LQ_PPL;
   // ---- staging: every cell's count and coverage start; of the staged cells' USED slots the records
   //      and the piece ends (a cell's first t_cnt of its LQ_PPL)
@@ -108,16 +118,16 @@ __global__ __launch_bounds__(EVAL_EVS, LQ_SCALAR_MIN_WAVES) void k_scalar(EvalAr
     const bool inv = act && !valid;
     const unsigned long long need = __ballot(valid && !cov);
     if (valid && !cov) {
-      st_wt4(a.fail_idx + (size_t)blk * EVAL_MAXB + 64 * EVAL_PASSES * wv + nlist +
+      st_wt4(a.fail_idx + rb * EVAL_MAXB + 64 * EVAL_PASSES * wv + nlist +
                  __popcll(need & ((1ull << lane) - 1ull)), i);
     }
     nlist += __popcll(need);
     n_inv += __popcll(__ballot(inv));
     n_ok += __popcll(__ballot(cov));
     if (inv) {
-      if (a.cost) st_ev8(a.cost + i, NAN);
-      if (a.w0) st_ev8(a.w0 + i, NAN);
-      if (a.status) a.status[i] = LOMPC_QP_INVALID;
+      if (acost) st_ev8(acost + i, NAN);
+      if (aw0) st_ev8(aw0 + i, NAN);
+      if (astatus) astatus[i] = LOMPC_QP_INVALID;
     } else if (cov) {
       const double2 q0 = *reinterpret_cast<const double2*>(s_cf + cfx(key, 0));
       const double2 q1 = *reinterpret_cast<const double2*>(s_cf + cfx(key, 2));
@@ -133,9 +143,9 @@ __global__ __launch_bounds__(EVAL_EVS, LQ_SCALAR_MIN_WAVES) void k_scalar(EvalAr
       acc_p0 += p0;
       acc_w0 += w0v;
       acc_err = fmax(acc_err, er);
-      if (a.cost) st_ev8(a.cost + i, cst);
-      if (a.w0) st_ev8(a.w0 + i, w0v);
-      if (a.status) a.status[i] = LOMPC_QP_OK;
+      if (acost) st_ev8(acost + i, cst);
+      if (aw0) st_ev8(aw0 + i, w0v);
+      if (astatus) astatus[i] = LOMPC_QP_OK;
     }
   }
   // ---- records: per-wave totals (fixed lane order), the workgroup's in wave order
@@ -152,7 +162,7 @@ __global__ __launch_bounds__(EVAL_EVS, LQ_SCALAR_MIN_WAVES) void k_scalar(EvalAr
       s_red[wv][PX_N_FAILED] = (double)nlist;
       s_red[wv][PX_N_INVALID] = (double)n_inv;
       s_red[wv][7] = tot[2];
-      st_wt4(a.fail_cnt + (size_t)blk * EVAL_WAVES + wv, nlist);
+      st_wt4(a.fail_cnt + rb * EVAL_WAVES + wv, nlist);
     }
   }
   __syncthreads();
@@ -164,6 +174,32 @@ __global__ __launch_bounds__(EVAL_EVS, LQ_SCALAR_MIN_WAVES) void k_scalar(EvalAr
       const int x = tid - N;
       for (int k = 0; k < EVAL_WAVES; ++k) v = x == PX_MAX_ERR ? fmax(v, s_red[k][x]) : v + s_red[k][x];
     }
-    st_wt8(a.partial + (size_t)blk * (N + NPX) + tid, v);
+    st_wt8(a.partial + rb * (N + NPX) + tid, v);
   }
+}
+
+__global__ __launch_bounds__(EVAL_EVS, LQ_SCALAR_MIN_WAVES) void k_scalar(EvalArgs a, int gs) {
+  if (a.skip && *a.skip) return;
+  scalar_block(a, gs, (int)blockIdx.x, RunOff{}, true);
+}
+
+// k_scalars: the scalar pass of the wide form (lompc_plan_run_steps with LOMPC_STEPS_SCALAR_PASS) — k_scalar's
+// work for the x.nruns runs of a path group in ONE launch, one workgroup per (run, block): workgroup
+// r x.nblk + b evaluates block b of run j = x.run0 + r from ring slot j % x.slots of the path tables, at run
+// j's prices, into record slot r (k_eval's layout, so k_closes closes the group).  Not persistent over the
+// runs: the pass is latency-bound (staging -> lookup -> stores) at a few KB of LDS, so the runs' workgroups
+// share the CUs four at a time instead of queueing behind each other in a loop.  The runs of a launch are
+// unordered: with one shared per-EV buffer (ev_stride 0) only run `last` (the call's last) stores per-EV
+// outputs, the NaN / INVALID of invalid EVs included; the earlier runs write records and re-solve lists
+// only (k_closes withholds their re-solved rows likewise).
+__global__ __launch_bounds__(EVAL_EVS, LQ_SCALAR_MIN_WAVES) void k_scalars(EvalArgs a, EvalsArgs x, int gs, int last) {
+  if (a.skip && *a.skip) return;
+  const int r = (int)blockIdx.x / x.nblk, b = (int)blockIdx.x - r * x.nblk, j = x.run0 + r;
+  RunOff ro;
+  ro.tab = (int64_t)(j % x.slots) * x.SG;
+  ro.rec = r * x.nblk;
+  ro.ev = (int64_t)j * x.ev_stride;
+  ro.lmbd = a.lmbd + (size_t)j * x.lm_stride;
+  ro.lmbd_r = a.lmbd_r + (size_t)j * x.lr_stride;
+  scalar_block(a, gs, b, ro, x.ev_stride != 0 || j == last);
 }

@@ -43,6 +43,7 @@ LOMPC_PLAN_SCALAR_PASS = 64
 LOMPC_PLAN_CELLS_SHIFT = 20
 LOMPC_STEPS_PER_KERNEL = 1
 LOMPC_STEPS_SPAN_EVENTS = 2
+LOMPC_STEPS_SCALAR_PASS = 4
 
 
 def LOMPC_PLAN_CELLS(g: int) -> int:

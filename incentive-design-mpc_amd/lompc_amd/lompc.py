@@ -581,7 +581,7 @@ class BatchPlan:
 
     def run_steps(self, lmbd, lmbd_r, n_runs: int, lmbd_stride: int, lmbd_r_stride: int = 0,
                   profile_every: int = 0, per_run_sets: bool = False, per_run: bool = False, out=None,
-                  per_kernel: bool = False, span_events: bool = False) -> dict:
+                  per_kernel: bool = False, span_events: bool = False, scalar_pass: bool = False) -> dict:
         """n_runs consecutive independent runs in ONE C-ABI call (lompc_plan_run_steps): run k at the
         prices lmbd + k lmbd_stride, lmbd_r + k lmbd_r_stride (device pointers or tensors, strides in
         doubles); profile_every > 0: only every E-th stepped launch carries the enabled HIP events.
@@ -592,22 +592,26 @@ class BatchPlan:
         cost / w0 / status (n_runs, B), sets as above).  out: a dict of preallocated per-run tensors for any of those keys (the others as the
         flags say).  per_kernel: LOMPC_STEPS_PER_KERNEL (the same runs, one part per launch, bit for
         bit the same outputs); span_events: one event pair over the stepped launches
-        (LOMPC_STEPS_SPAN_EVENTS)."""
+        (LOMPC_STEPS_SPAN_EVENTS); scalar_pass: LOMPC_STEPS_SCALAR_PASS, the wide scalar form (k_scalars: per-EV
+        cost / w0 / status and set_stats from the coefficient records alone) — plans built with
+        scalar_pass=True only (ValueError otherwise)."""
         call, res = self.steps_call(lmbd, lmbd_r, n_runs, lmbd_stride, lmbd_r_stride, profile_every=profile_every,
                                     per_run_sets=per_run_sets, per_run=per_run, out=out, per_kernel=per_kernel,
-                                    span_events=span_events)
+                                    span_events=span_events, scalar_pass=scalar_pass)
         call()
         return res
 
     def steps_call(self, lmbd, lmbd_r, n_runs: int, lmbd_stride: int, lmbd_r_stride: int = 0,
                    profile_every: int = 0, per_run_sets: bool = False, per_run: bool = False, out=None,
-                   per_kernel: bool = False, span_events: bool = False):
+                   per_kernel: bool = False, span_events: bool = False, scalar_pass: bool = False):
         """run_steps prepared: (call, outputs) — ``call()`` issues the same lompc_plan_run_steps with
         every argument already converted (no Python work between the caller's clock and the C-ABI
         entry beyond one ctypes call); it may be called again for the same runs into the same
         outputs."""
         if self.direct:
             raise ValueError("run_steps: PATH-mode plans only")
+        if scalar_pass and not self.scalar_pass:
+            raise ValueError("run_steps: scalar_pass=True needs a plan built with scalar_pass=True")
         self._usable()
         torch = _torch()
         K = int(n_runs)
@@ -638,9 +642,11 @@ class BatchPlan:
         ev_stride = self.B if per_ev and strided[0] else 0
         sw_stride = self.S * self.N if res["set_sum_w"] is not None and res["set_sum_w"].dim() == 3 else 0
         st_stride = self.S * _lib.LOMPC_SET_STATS if res["set_stats"] is not None and res["set_stats"].dim() == 3 else 0
-        if (res["set_sum_w"] is None) != (res["set_stats"] is None) or (sw_stride == 0) != (st_stride == 0):
+        # (a scalar_pass plan has set_stats and no set_sum_w)
+        if not self.scalar_pass and ((res["set_sum_w"] is None) != (res["set_stats"] is None) or (sw_stride == 0) != (st_stride == 0)):
             raise ValueError("run_steps: set_sum_w and set_stats are both per run or both shared")
-        flags = (_lib.LOMPC_STEPS_PER_KERNEL if per_kernel else 0) | (_lib.LOMPC_STEPS_SPAN_EVENTS if span_events else 0)
+        flags = (_lib.LOMPC_STEPS_PER_KERNEL if per_kernel else 0) | (_lib.LOMPC_STEPS_SPAN_EVENTS if span_events else 0) \
+            | (_lib.LOMPC_STEPS_SCALAR_PASS if scalar_pass else 0)
         ptrs = [_ptr(res[k]) for k in keys]
         fn = self._lib.lompc_plan_run_steps
         args = (self._plan, pl, int(lmbd_stride), pr, int(lmbd_r_stride), K, int(profile_every), *ptrs, sw_stride,

@@ -108,6 +108,8 @@ class PriceSolver:
         self.reserve_evs = 0  # > 0: the loop plans' workspaces sized for this many EVs (BatchPlan.reserve)
         self._plan_w0 = None
         self._w0_live = False
+        self._plan_w0m = None  # get_w0_price0_many's scalar-pass plan
+        self._w0m_live = False
         self._staged = {}  # partition -> its loop plan and levels (stage_partition / use_partition)
         self._A_bar = None
         self._A_bar_inv = None
@@ -283,7 +285,7 @@ class PriceSolver:
         """Make the plan and levels staged for partition p current (set_charge_levels done)."""
         for k, v in self._staged[p].items():
             setattr(self, k, v)
-        self._w0_live = False
+        self._w0_live = self._w0m_live = False
 
     def _build_plans(self, gamma, presorted: bool = False, prebuilt=None) -> None:
         """Batch layout of one price iteration: set 0 = this rank's EVs, set 1 = the central QP.
@@ -332,7 +334,7 @@ class PriceSolver:
                 self._plan.set_comm(comm)
         else:
             self._plan.update(self._gam, off, w_ref=self._wr2, validate=False)
-        self._w0_live = False  # the w0 plan follows lazily (get_w0_price0_device)
+        self._w0_live = self._w0m_live = False  # the w0 plans follow lazily (get_w0_price0_device / _many_device)
         self._B = B
 
 
@@ -698,3 +700,46 @@ class PriceSolver:
         st = st.cpu().numpy()
         self._check_stats(st)
         return w0, float(st[0, _lib.LOMPC_STAT_SUM_PRICE0])
+
+    def get_w0_price0_many(self, lmbds: np.ndarray, lmbd_r: float) -> tuple[np.ndarray, np.ndarray]:
+        """get_w0_price0 at K price vectors ``lmbds`` (K, r) — a tariff comparison, a sensitivity sweep:
+        (w0 (K, nEVs of this rank), mean price0 (K,)).  Row k equals get_w0_price0(lmbds[k], lmbd_r): w0 bit
+        for bit, price0 to the rounding of its sum."""
+        w0, price0_sums = self.get_w0_price0_many_device(lmbds, lmbd_r)
+        K = len(price0_sums)
+        return (w0.cpu().numpy() if w0 is not None else np.zeros((K, 0))), price0_sums / self.nEVs
+
+    @_solver_stream
+    def get_w0_price0_many_device(self, lmbds: np.ndarray, lmbd_r: float):
+        """(w0 device tensor (K, EVs of this rank), the K global sums of price0) — no host copy of w0.  ONE
+        run_steps(scalar_pass=True) call over a scalar-pass plan on the solver's gamma: the K evaluations in
+        one k_scalars launch per group of runs (LOMPC_STEPS_SCALAR_PASS), every run's w0 at its own row and
+        its own set_stats.  A sharded solver takes K get_w0_price0_device calls (the scalar pass does not run
+        with a communicator)."""
+        torch = _torch()
+        lmbds = np.asarray(lmbds, dtype=np.float64)
+        if lmbds.ndim != 2 or lmbds.shape[1] != self.r:
+            raise ValueError(f"get_w0_price0_many: lmbds must have shape (K, {self.r})")
+        K, B = lmbds.shape[0], self._B
+        if self.group is not None or not B or not K:
+            res = [self.get_w0_price0_device(lmbds[k], lmbd_r) for k in range(K)]
+            w0 = torch.stack([r[0] for r in res]) if K and res[0][0] is not None else None
+            return w0, np.array([r[1] for r in res], dtype=np.float64)
+        off = np.array([0, B], dtype=np.int64)
+        if not self._w0m_live:
+            if self._plan_w0m is None:
+                self._plan_w0m = BatchPlan(self.lompc, self._gam_w0, off, want_w=False, want_cost=False, want_w0=True,
+                                           want_set=True, validate=False, scalar_pass=True)
+            else:
+                self._plan_w0m.update(self._gam_w0, off, validate=False)
+            self._w0m_live = True
+        N3 = 3 * self.N
+        h = np.zeros((K, N3 + 1))
+        h[:, : self.r] = lmbds
+        h[:, N3] = float(lmbd_r)
+        d = torch.as_tensor(h).to(self._dev)  # [K][3N prices | lmbd_r]
+        out = self._plan_w0m.run_steps(d, d[:, N3:], K, N3 + 1, N3 + 1, per_run=True, scalar_pass=True)
+        st = out["set_stats"].cpu().numpy()  # (K, 1, 8)
+        for k in range(K):
+            self._check_stats(st[k])
+        return out["w0"], st[:, 0, _lib.LOMPC_STAT_SUM_PRICE0].copy()

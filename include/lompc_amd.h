@@ -208,7 +208,8 @@ typedef struct lompc_plan lompc_plan;
                                      (those stay O(pieces)).  In every other case, and in every other entry
                                      point (lompc_plan_run_steps, lompc_plan_run_chain, lompc_price_loop,
                                      lompc_solve_batch, lompc_run), a flagged plan behaves exactly as an
-                                     unflagged one.  Contract: per-EV cost, w0 and status carry the same bits
+                                     unflagged one — but for a lompc_plan_run_steps call that asks for the
+                                     pass itself (LOMPC_STEPS_SCALAR_PASS, below).  Contract: per-EV cost, w0 and status carry the same bits
                                      as the default evaluation's (the same lookup and fma forms; EVs no staged
                                      piece covers take the same certified re-solve); the set_stats sums
                                      (SUM_W0, SUM_PRICE0, SUM_COST) are summed in another fixed order, so they
@@ -287,9 +288,36 @@ int lompc_plan_run(lompc_plan* plan, const double* lmbd, const double* lmbd_r, d
  *   LOMPC_STEPS_SPAN_EVENTS the enabled K_EVAL timing as ONE event pair (wide form: around the first
  *                           group's evaluation launch, read back as its runs; stepped form: from the
  *                           start of the first full stepped launch to the end of the last, read back
- *                           as that many launches) — no per-launch event boundaries inside the steps */
+ *                           as that many launches) — no per-launch event boundaries inside the steps
+ *   LOMPC_STEPS_SCALAR_PASS the wide SCALAR form: the wide form's three launches per group with k_scalars as
+ *                           the evaluation — k_scalar's pass (LOMPC_PLAN_SCALAR_PASS) for the group's runs, one
+ *                           workgroup per (run, block), from the coefficient records alone; the call shape of
+ *                           PriceSolver.get_w0_price0 at K price vectors.  Opt-in per call; without the flag
+ *                           every call behaves as before.  The call takes the form exactly when ALL hold: this
+ *                           flag is given; the plan was created with LOMPC_PLAN_SCALAR_PASS and without
+ *                           LOMPC_PLAN_DIAG_REPAIR; the plan takes the wide schedule (no LOMPC_PLAN_WARM_START,
+ *                           and its tables fit the wide form's ring); w == NULL and set_sum_w == NULL; at
+ *                           least one of cost, w0, status, set_stats is non-NULL; no communicator is
+ *                           attached; the plan has at least one EV; and the run is not the aggregation of a
+ *                           LOMPC_PLAN_SORTED_GAMMA plan with no per-EV output (those stay O(pieces)).  The
+ *                           flag on a plan created without LOMPC_PLAN_SCALAR_PASS is a misuse:
+ *                           LOMPC_ERR_INVALID_ARG with an error text, nothing launched or written.  When only
+ *                           a per-call condition fails (w or set_sum_w given, a communicator, a warm-started
+ *                           or DIAG_REPAIR plan) the call runs exactly as without the flag: the same kernels,
+ *                           the same bits.  Contract as LOMPC_PLAN_SCALAR_PASS's: per-EV cost, w0 and status
+ *                           carry the bits of the flagless call and of one scalar lompc_plan_run per run; the
+ *                           set_stats sums are summed per block in another fixed order, so they equal the
+ *                           flagless call's to rounding and are the same bits in every call on the same
+ *                           inputs, whatever the group split; counts and MAX_ERR as the flagless call.  With
+ *                           ev_stride = 0 only the call's last run stores per-EV outputs (the runs of a
+ *                           launch are unordered).  Combined with LOMPC_STEPS_PER_KERNEL: the same kernels,
+ *                           one run per group, the same bits.  Profiling: the evaluation launch is recorded
+ *                           under LOMPC_PLAN_K_SCALAR as its runs, and no LOMPC_PLAN_K_EVAL launch is (the group's
+ *                           path launch is read as its runs too: K_PATH, K_SCALAR and K_FINAL all count K);
+ *                           LOMPC_STEPS_SPAN_EVENTS keeps its meaning (the first group's evaluation launch). */
 #define LOMPC_STEPS_PER_KERNEL 1
 #define LOMPC_STEPS_SPAN_EVENTS 2
+#define LOMPC_STEPS_SCALAR_PASS 4
 int lompc_plan_run_steps(lompc_plan* plan, const double* lmbd, int64_t lmbd_stride,
                          const double* lmbd_r, int64_t lmbd_r_stride, int n_runs,
                          int profile_every, double* w, double* cost, double* w0, int8_t* status,

@@ -159,6 +159,7 @@ struct lompc_plan {
     int* rfcnt = nullptr;         // slots of a path group, [runs][nblk][...]
     int* rfidx = nullptr;
     int64_t cap_rrec = 0;         // their capacity in blocks (runs x nblk)
+    int64_t tail_launches = 0;    // k_evals_tail launches issued so far (lompc_plan_get_tail_launches)
   } stp;
   int* d_errflag = nullptr;
   unsigned long long* d_tally = nullptr;  // [3] EVs repaired / failed / invalid over every run since

@@ -1936,6 +1936,93 @@ __global__ __launch_bounds__(EVAL_EVS, EVAL_MIN_WAVES) void k_evals(EvalArgs a, 
   }
 }
 
+// k_evals' runs for k_evals_tail's evaluation workgroups (b: the block): the same eval_block calls on the same RunOff,
+// with k_evals' idioms (the argument structs re-read from the argument segment per run, where they sit at offsets
+// 0 and KARG_X as in k_evals; the block index laundered per run), without its diagnostic builds' branches.  A
+// copy, not a shared body: k_evals calling a common function kept its instruction counts but came out in another
+// order, and k_evals stays the measured kernel, instruction for instruction
+template <int NT>
+__device__ __forceinline__ void evals_runs(const EvalArgs& a, const EvalsArgs& x_, const int b) {
+  for (int r = 0; r < x_.nruns; ++r) {
+#if LQ_EVALS_KARGS
+    typedef __attribute__((address_space(4))) const EvalArgs karg_t;
+    typedef __attribute__((address_space(4))) const EvalsArgs kargx_t;
+    typedef __attribute__((address_space(4))) const char kargc_t;
+    karg_t* ka = (karg_t*)__builtin_amdgcn_kernarg_segment_ptr();
+    asm volatile("" : "+s"(ka));
+    const EvalArgs& ar = *(const EvalArgs*)ka;
+    const EvalsArgs& x = *(const EvalsArgs*)(kargx_t*)((kargc_t*)ka + KARG_X);
+#else
+    const EvalArgs& ar = a;
+    const EvalsArgs& x = x_;
+#endif
+    const int j = x.run0 + r;
+    RunOff ro;
+    ro.tab = (int64_t)(j % x.slots) * x.SG;
+    ro.rec = r * x.nblk;
+    ro.ev = (int64_t)j * x.ev_stride;
+    ro.lmbd = ar.lmbd + (size_t)j * x.lm_stride;
+    ro.lmbd_r = ar.lmbd_r + (size_t)j * x.lr_stride;
+    ro.launder = true;
+    ro.gamma_lds = r > 0;
+    ro.pipelined = LQ_EVALS_PIPELINED;
+    ro.first = r == 0;
+    int bl = b;
+    asm volatile("" : "+s"(bl));
+    eval_block<NT, false>(ar, bl, nullptr, ro);
+#if LQ_EVALS_RUN_BARRIER
+    __syncthreads();
+#endif
+  }
+}
+
+// The wide form's fused launch (LQ_WIDE_TAIL_PATHS): group g's evaluations and, BEHIND them in grid order, group
+// g + 1's paths.  Workgroups [0, x_.nblk) are k_evals' (evals_runs: the same eval_block calls on the same RunOff).
+// Workgroups [nblk, nblk + npw) are path workgroups laid out as k_step's: LQ_STEP_CELLS cells of one set, one per
+// wave (G % LQ_STEP_CELLS == 0), of LQ_TAIL_RUNS runs each (runs r < np of the next group; the waves left over return
+// at once), the box table's barrier stays inside the set; run run0p + r's tables go to ring slot (run0p + r) %
+// slots as k_paths writes them.  The
+// evaluation workgroups fill the chip in one dispatch round, so the path workgroups are dispatched as evaluation
+// workgroups retire and run in the launch's tail, which otherwise idles; no workgroup waits for another and the
+// two kinds share no memory (the ring holds both groups: no run of group g uses a slot of group g + 1), so any
+// dispatch order gives the same results.  The path waves keep the default issue priority: beside them the
+// evaluation's last waves are the launch's critical path.
+#ifndef LQ_TAIL_RUNS
+// k_evals_tail: runs per path workgroup, the same LQ_STEP_CELLS cells of each (1: k_step's layout, the upper waves
+// return at once; EVAL_WAVES / LQ_STEP_CELLS = 2: every wave a path — one set's box table serves both runs).  A
+// workgroup is dispatched with all its waves' registers, so of the layout with 1 run a CU holds three workgroups
+// (12 path waves), of the layout with 2 runs two (16 path waves, k_paths' own occupancy): 36 runs of 96 cells are
+// 864 workgroups over 768 places (two rounds) against 432 over 512 (one).  Measured at 100 steps: 9.85 (9.80-9.91)
+// against 9.93 (9.82-9.96) us per step, the fused launch 9.11 against 9.19 us per run (profiles/r08)
+#define LQ_TAIL_RUNS (EVAL_WAVES / LQ_STEP_CELLS)
+#endif
+static_assert(LQ_TAIL_RUNS >= 1 && LQ_TAIL_RUNS * LQ_STEP_CELLS <= EVAL_WAVES, "k_evals_tail: one path per wave");
+template <int NT>
+__global__ __launch_bounds__(EVAL_EVS, EVAL_MIN_WAVES) void k_evals_tail(EvalArgs a, EvalsArgs x_, PathArgs pa, int run0p,
+                                                                          int np) {
+  const int q = (int)blockIdx.x - x_.nblk;
+  if (q < 0) {
+    evals_runs<NT>(a, x_, (int)blockIdx.x);
+    return;
+  }
+  const int wv = (int)(threadIdx.x >> 6), wr = wv / LQ_STEP_CELLS;  // the wave's run of the workgroup's
+  const int SG = (int)x_.SG, wpr = SG / LQ_STEP_CELLS;              // path workgroups per LQ_TAIL_RUNS runs
+  const int r = q / wpr * LQ_TAIL_RUNS + wr, cell = (q % wpr) * LQ_STEP_CELLS + (wv - wr * LQ_STEP_CELLS);
+  if (wr >= LQ_TAIL_RUNS || r >= np) return;
+  const int j = run0p + r;
+  const int64_t o = (int64_t)(j % x_.slots) * SG;
+  PathArgs b = pa;
+  b.lmbd = pa.lmbd + (size_t)j * x_.lm_stride;
+  b.lmbd_r = pa.lmbd_r + (size_t)j * x_.lr_stride;
+  b.t_cnt = pa.t_cnt + o;
+  b.t_lo = pa.t_lo + o;
+  b.t_sl = pa.t_sl + o * 64;
+  b.t_ge = pa.t_ge + o * LQ_PPL;
+  b.t_cf = pa.t_cf + o * LQ_PPL * 8;
+  b.t_ab = pa.t_ab + o * LQ_PPL * pa.N;
+  path_cell<NT, true>(b, cell);
+}
+
 // k_evals with the stager (LQ_EVALS_STAGER; compact tables, a.cap = their capacity, a.G <= 64, N + 4
 // <= 64, blocks of <= LQ_EVALS_MAXB EVs): wave LQ_EVALS_RW stages run 0's table, then during run r the
 // table of run r + 1 into the other LDS table while waves 0 .. LQ_EVALS_RW - 1 evaluate run r (eval_block
@@ -2013,6 +2100,16 @@ EvalsKernel evals_st_kernel(int N) {
     case 24: return k_evals_st<24>;
     case 48: return k_evals_st<48>;
     default: return k_evals_st<0>;
+  }
+}
+typedef void (*EvalsTailKernel)(EvalArgs, EvalsArgs, PathArgs, int, int);
+EvalsTailKernel evals_tail_kernel(int N) {
+  switch (N) {
+    case 12: return k_evals_tail<12>;
+    case 16: return k_evals_tail<16>;
+    case 24: return k_evals_tail<24>;
+    case 48: return k_evals_tail<48>;
+    default: return k_evals_tail<0>;
   }
 }
 EvalsKernel evals_kernel(int N) {
@@ -3589,10 +3686,14 @@ int stepped_setup(lompc_plan* p, hipStream_t st, bool wide) {
 }
 
 #ifndef LQ_WIDE_RUNS
-#define LQ_WIDE_RUNS 64                 // wide form: runs per path launch (its table ring holds one more; 64: 13.96
+#define LQ_WIDE_RUNS 64                 // wide form: runs per path launch (its table ring: wide_slots; 64: 13.96
                                         // vs 14.32 us per step over 64 steps with 32 — the paths' launch tail amortised)
 #endif
 #define LQ_WIDE_BYTES (1ll << 30)        // wide form: the table ring's memory at most
+#ifndef LQ_WIDE_TAIL_PATHS
+#define LQ_WIDE_TAIL_PATHS 1            // wide form: group g + 1's paths behind group g's evaluations in ONE launch
+                                        // (k_evals_tail; 0: a k_paths launch before every group's k_evals)
+#endif
 
 // The wide form's runs per path launch for K runs: bounded by the table ring's memory
 // (LQ_WIDE_BYTES) and the grid (fit: the most the plan allows; < 1: the plan is too big for two slots)
@@ -3602,6 +3703,14 @@ int64_t wide_fit(const lompc_plan* p) {
   return std::min<int64_t>(LQ_WIDE_BYTES / (ncell * cell_bytes), INT32_MAX / 64 / ncell) - 1;
 }
 
+// The ring's slots for groups of grp runs: 2 grp where the plan allows them (wide_fit + 1 slots at most) — TWO
+// groups at once, so that group g + 1's paths can be written while group g is evaluated (k_evals_tail): runs
+// g grp .. (g + 2) grp - 1 are 2 grp consecutive j, so their slots j % (2 grp) never collide, and group g + 2's
+// paths rewrite group g's slots only after group g has closed.  Else grp + 1 (one group and the next run).
+int64_t wide_slots(const lompc_plan* p, int64_t grp) {
+  return LQ_WIDE_TAIL_PATHS && 2 * grp <= wide_fit(p) + 1 ? 2 * grp : grp + 1;
+}
+
 // the wide form's table ring, sized for the largest group the plan allows whatever this call's K (a
 // later call with more runs must not reallocate — hipMalloc / hipFree synchronise the device)
 int wide_ring(lompc_plan* p, hipStream_t st) {
@@ -3609,7 +3718,7 @@ int wide_ring(lompc_plan* p, hipStream_t st) {
   int rc;
   const int N = p->N;
   const int64_t ncell = p->S * p->G;
-  const int64_t ring = (std::min<int64_t>(LQ_WIDE_RUNS, wide_fit(p)) + 1) * ncell;
+  const int64_t ring = wide_slots(p, std::min<int64_t>(LQ_WIDE_RUNS, wide_fit(p))) * ncell;
   if (ring > z.cap_wt) {
     auto& t = z.wt;
     const int64_t c = ring;
@@ -3715,6 +3824,7 @@ int lq_run_steps_stepped(lompc_plan* p, const double* lmbd, int64_t lmbd_stride,
     // batched: per path group of n <= Kc runs THREE launches — k_paths (the n paths), k_evals (the n
     // evaluations, each workgroup through its block of every run) and k_closes (the n x S closings);
     // the same kernels' arithmetic as the split form below, so the same bits
+    // (tail, below: from the second group on the paths ride in the launch before, k_evals_tail)
     // (scalar — LOMPC_STEPS_SCALAR_PASS, the rule of lompc_amd.h: k_scalars instead of k_evals, one workgroup
     // per (run, block) on the same block map and record slots, timed as K_SCALAR)
     // record slots x blocks, bounded like the table ring: a run's slot holds every block's record, its
@@ -3755,9 +3865,17 @@ int lq_run_steps_stepped(lompc_plan* p, const double* lmbd, int64_t lmbd_stride,
     const int grp = split ? 1 : (int)std::min<int64_t>(Kc, kr);
     if (z.stg) ea.cap = std::min(LQ_EVALS_CAP, p->G * LQ_PPL);
     const size_t lds_e = z.stg ? evals_st_lds(N, p->G, ea.cap) : lds;
+    // tail (LQ_WIDE_TAIL_PATHS): with a second group, and a ring that holds two groups (wide_slots; the ring is
+    // sized for the plan's largest group, which a smaller group's two may still exceed), group g + 1's paths
+    // ride behind group g's evaluations in one k_evals_tail launch: k_paths(group 0), then per group
+    // k_evals_tail (the last group: k_evals) and k_closes.  Else a k_paths launch before every k_evals.
+    const bool tail = LQ_WIDE_TAIL_PATHS && !split && !scalar && !z.stg && K > grp && p->G % LQ_STEP_CELLS == 0 &&
+                      wide_slots(p, grp) == 2 * (int64_t)grp && 2 * (int64_t)grp * ncell <= z.cap_wt;
+    const int slots = tail ? 2 * grp : Kc + 1;
     for (int g0 = 0; g0 < K; g0 += grp) {
       const int n = std::min(grp, K - g0);
-      {
+      const int np = tail ? std::max(0, std::min(grp, K - g0 - grp)) : 0;  // the next group's runs, behind this one's
+      if (!tail || g0 == 0) {
         PathArgs pw = path_args(p, lmbd, lmbd_r, z.wt);
         hipEvent_t e0 = nullptr, e1 = nullptr;
         if (plan_prof_begin(p, LOMPC_PLAN_K_PATH, &e0, &e1)) return fail_arg(p, "profiling events");
@@ -3772,10 +3890,18 @@ int lq_run_steps_stepped(lompc_plan* p, const double* lmbd, int64_t lmbd_stride,
         const int kk = scalar ? LOMPC_PLAN_K_SCALAR : LOMPC_PLAN_K_EVAL;
         if (ev && plan_prof_begin(p, kk, &e0, &e1)) return fail_arg(p, "profiling events");
         const EvalsArgs x{g0, n, slots, z.nblk, lmbd_stride, lmbd_r_stride, ev_stride, ncell};
-        if (scalar)
+        if (scalar) {
           hipExtLaunchKernelGGL(k_scalars, dim3((unsigned)(n * z.nblk)), dim3(EVAL_EVS), scalar_lds(p->G, p->scalar_cells), st,
                                 e0, e1, 0, ea, x, p->scalar_cells, K - 1);
-        else
+        } else if (np > 0) {
+          // (the next group's paths are counted as a K_PATH launch, their time is inside this launch's events)
+          const PathArgs pw = path_args(p, lmbd, lmbd_r, z.wt);
+          const int64_t npw = (int64_t)((np + LQ_TAIL_RUNS - 1) / LQ_TAIL_RUNS) * (ncell / LQ_STEP_CELLS);
+          hipExtLaunchKernelGGL(evals_tail_kernel(N), dim3((unsigned)(z.nblk + npw)), dim3(EVAL_EVS), lds_e, st, e0, e1, 0, ea,
+                                x, pw, g0 + grp, np);
+          if ((p->prof >> LOMPC_PLAN_K_PATH) & 1) p->prof_n[LOMPC_PLAN_K_PATH] += 1;
+          z.tail_launches += 1;
+        } else
           hipExtLaunchKernelGGL(z.stg ? evals_st_kernel(N) : evals_kernel(N), dim3((unsigned)z.nblk), dim3(EVAL_EVS), lds_e, st,
                                 e0, e1, 0, ea, x);
         HIPCHK(p, hipGetLastError());
@@ -4085,6 +4211,13 @@ int lompc_plan_get_info(const lompc_plan* p, int64_t* B, int64_t* S, int* cells,
   if (S) *S = p->S;
   if (cells) *cells = p->G;
   if (eval_workgroups) *eval_workgroups = p->nblk;
+  return LOMPC_OK;
+}
+
+int lompc_plan_get_wide_info(const lompc_plan* p, int64_t* ring_runs, int64_t* tail_launches) {
+  if (!p) return LOMPC_ERR_INVALID_ARG;
+  if (ring_runs) *ring_runs = std::max<int64_t>(0, wide_fit(p) + 1);
+  if (tail_launches) *tail_launches = p->stp.tail_launches;
   return LOMPC_OK;
 }
 

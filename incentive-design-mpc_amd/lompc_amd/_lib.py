@@ -101,6 +101,7 @@ SIGNATURES = [
     ("lompc_levels_stats", _I, [_P, _L, _P, _I, _P, _P, ctypes.POINTER(ctypes.c_size_t), _P]),
     ("lompc_plan_status", _I, [_P, _P, _P, _P, _P]),
     ("lompc_plan_get_info", _I, [_P, _P, _P, _P, _P, _P]),
+    ("lompc_plan_get_wide_info", _I, [_P, _P, _P]),
     ("lompc_plan_update", _I, [_P, _L, _P, _P, _P, _P]),
     ("lompc_plan_reserve", _I, [_P, _L]),
     ("lompc_price_loop", _I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),

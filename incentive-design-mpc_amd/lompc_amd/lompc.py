@@ -504,14 +504,21 @@ class BatchPlan:
     def info(self) -> dict:
         """Batch size, parameter sets, gamma cells per set, k_eval workgroups of the plan, the runs per
         stepped run_steps launch (1 once the stepped form has run, else 0) and whether run_steps' wide
-        form evaluates through k_evals_st (the stager wave: set reductions grouped by seven row waves)."""
+        form evaluates through k_evals_st (the stager wave: set reductions grouped by seven row waves);
+        ring_runs: the runs whose path tables the wide form's table ring may hold at once; tail_launches: the
+        fused launches of its run_steps calls so far (k_evals_tail: a group's evaluations with the next
+        group's paths behind them; 0 where every group took its own k_paths launch)."""
         if self.direct:
-            return {"B": self.B, "sets": self.S, "cells": 0, "workgroups": 0, "steps_group": 0, "evals_staged": False}
+            return {"B": self.B, "sets": self.S, "cells": 0, "workgroups": 0, "steps_group": 0, "evals_staged": False,
+                    "ring_runs": 0, "tail_launches": 0}
         B, S, cells, wg, grp = ctypes.c_int64(0), ctypes.c_int64(0), ctypes.c_int(0), ctypes.c_int(0), ctypes.c_int(0)
         self._check_rc(self._lib.lompc_plan_get_info(self._plan, ctypes.byref(B), ctypes.byref(S), ctypes.byref(cells),
                                                      ctypes.byref(wg), ctypes.byref(grp)))
+        ring, tail = ctypes.c_int64(0), ctypes.c_int64(0)
+        self._check_rc(self._lib.lompc_plan_get_wide_info(self._plan, ctypes.byref(ring), ctypes.byref(tail)))
         return {"B": B.value, "sets": S.value, "cells": cells.value, "workgroups": wg.value,
-                "steps_group": min(grp.value, 1), "evals_staged": grp.value == 2}
+                "steps_group": min(grp.value, 1), "evals_staged": grp.value == 2, "ring_runs": ring.value,
+                "tail_launches": tail.value}
 
     def update(self, gamma, set_offsets, w_ref=None, validate=True) -> "BatchPlan":
         """Re-target the plan at a new batch with the same contexts and set counts (e.g. the

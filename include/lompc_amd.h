@@ -389,6 +389,13 @@ int lompc_plan_status(lompc_plan* plan, void* stream, int64_t* n_repaired,
 int lompc_plan_get_info(const lompc_plan* plan, int64_t* B, int64_t* S, int* cells, int* eval_workgroups,
                         int* steps_group);
 
+/* The wide form of lompc_plan_run_steps (plans without warm starts).  ring_runs: the runs whose path tables the
+ * plan's table ring may hold at once (its memory bound over the plan's cells).  tail_launches: the fused launches
+ * issued since the plan's creation — with a second group of runs the wide form carries group g + 1's paths
+ * behind group g's evaluations in one launch (k_evals_tail) where the ring holds two groups (ring_runs >= twice
+ * the group's runs); 0 where every group took its own path launch.  Either pointer may be null. */
+int lompc_plan_get_wide_info(const lompc_plan* plan, int64_t* ring_runs, int64_t* tail_launches);
+
 /* HIP-event timing of the plan's kernels (hipExtLaunchKernel start/stop events on their own
  * dispatches): enable takes a mask of (1 << LOMPC_PLAN_K_*) bits (0 = off); read synchronises
  * and returns one kernel's accumulated milliseconds and launch count since the last reset. */

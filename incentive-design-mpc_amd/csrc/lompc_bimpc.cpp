@@ -656,8 +656,18 @@ static bool prune_dependent(const std::vector<double>& S, int nJ, std::vector<in
 bool polish(const Bimpc& B, std::vector<double>& z, std::vector<double>& llo, std::vector<double>& lhi,
             std::vector<double>& lg, const std::vector<double>& sg) {
   const int N = B.N, nb = B.nb, n = B.n, mg = B.mg;
+  // a block with no weight and no coupling coefficient (WEIGHTED cost, empty partition: omega =
+  // theta^2 Mp^2 = 0 and c_k = -theta Mp = 0) appears in neither the objective nor the coupling rows: its
+  // variables are free, their reduced Hessian is the zero matrix (no Cholesky) and their gradient is 0 —
+  // they keep the interior point's values and take no part in the equality-constrained solves
+  std::vector<char> dead(nb, 0);
+  for (int k = 0; k < nb; ++k) {
+    dead[k] = B.ck[k] == 0.0;
+    for (int t = 0; t < N && dead[k]; ++t) dead[k] = B.omega[k * N + t] == 0.0;
+  }
   std::vector<int> fix(n, 0);  // -1 at the lower bound, +1 at the upper bound, 0 free
   for (int i = 0; i < n; ++i) {
+    if (i < nb * N && dead[i / N]) continue;
     if (llo[i] > z[i])
       fix[i] = -1;
     else if (lhi[i] > B.ub[i] - z[i])
@@ -672,11 +682,18 @@ bool polish(const Bimpc& B, std::vector<double>& z, std::vector<double>& llo, st
   int nJ = 0;
   std::vector<double> lgn, tN(N), tn(n), llon, lhin;
   for (int outer = 0;; ++outer) {
-  if (outer >= 8) PFAIL("active set");
+  // the first eight passes release every wrong-sign multiplier at once; where that cycles (the exp weights'
+  // nearly flat directions: a dozen lower bounds released together, all fixed again two rounds later, the
+  // same set four passes on) the later passes release ONE, the worst row or else the worst bound, as a
+  // primal active-set method does
+  const bool single = outer >= 8;
+  if (outer >= 8 + 4 * N) PFAIL("active set");
   bool feasible = false;
   // rounds: a free variable that leaves its box is fixed at that bound, a violated coupling row
   // joins the active set, and the equality-constrained problem is solved again
-  for (int round = 0, prunes = 0; round < 6 && !feasible; ++round) {
+  // (up to 6 + 2N rounds: with the exp weights a violated lower bound can hand its violation on to the
+  // neighbouring stage, one stage per round)
+  for (int round = 0, prunes = 0; round < 6 + 2 * N && !feasible; ++round) {
     bool pruned = false;
     nJ = (int)J.size();
     Ej.assign((size_t)nJ * N, 0.0);  // active rows of E = [-I; I; -A; A]
@@ -705,6 +722,7 @@ bool polish(const Bimpc& B, std::vector<double>& z, std::vector<double>& llo, st
       std::vector<std::vector<int>> F(nb + 1);
       std::vector<int> bad(nb + 1, 0);  // 1: u <= 0, 2: chol
       BlockPool::get().run(nb + 1, [&](int k) {
+        if (k < nb && dead[k]) return;
         for (int t = 0; t < N; ++t)
           if (!fix[k * N + t]) F[k].push_back(t);
         const int m = (int)F[k].size();
@@ -823,8 +841,12 @@ bool polish(const Bimpc& B, std::vector<double>& z, std::vector<double>& llo, st
   bool changed = false;
   lgn.assign(mg, 0.0);
   std::vector<int> Jn;
+  int worst = -1;
+  if (single)
+    for (int a = 0; a < nJ; ++a)
+      if (nu[a] < -dtol && (worst < 0 || nu[a] < nu[worst])) worst = a;
   for (int a = 0; a < nJ; ++a) {
-    if (nu[a] < -dtol) {
+    if (nu[a] < -dtol && (!single || a == worst)) {
       changed = true;
       continue;
     }
@@ -841,8 +863,22 @@ bool polish(const Bimpc& B, std::vector<double>& z, std::vector<double>& llo, st
   mulLt(B, tN.data(), tn.data());
   llon.assign(n, 0.0);
   lhin.assign(n, 0.0);
+  int wv = -1;  // (single: the fixed variable whose multiplier has the wrong sign by the most)
+  double wr = dtol;
+  if (single)
+    for (int i = 0; i < n; ++i) {
+      const double bad = fix[i] < 0 ? -(g[i] + tn[i]) : (fix[i] > 0 ? g[i] + tn[i] : 0.0);
+      if (bad > wr) {
+        wr = bad;
+        wv = i;
+      }
+    }
   for (int i = 0; i < n; ++i) {
     const double r = g[i] + tn[i];  // = llo - lhi at a KKT point
+    if (single && fix[i] && i != wv) {  // (kept fixed this pass, whatever its sign)
+      (fix[i] < 0 ? llon[i] : lhin[i]) = std::max(fix[i] < 0 ? r : -r, 0.0);
+      continue;
+    }
     if (fix[i] < 0) {
       if (r < -dtol) {
         fix[i] = 0;

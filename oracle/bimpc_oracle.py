@@ -209,9 +209,18 @@ class BiMPCLiteral:
         c_g = self.bi["c_g"]
         s = h - G @ z
         act = np.where(lam > s)[0]
-        for _outer in range(10):  # active-set corrections: add violated rows, drop wrong-sign ones
+        # a variable with no curvature and no coupling coefficient (WEIGHTED cost, empty partition) is in
+        # no equation: a unit diagonal keeps the KKT matrix regular and the variable where it is (its
+        # gradient is 0), instead of a least-squares solve of a singular system at 1e-12 accuracy
+        free = ~np.any(Hq != 0.0, axis=0) & ~np.any(G[2 * n:] != 0.0, axis=0)
+        free[2 * self.P * N:] = False
+        Hq = Hq + np.diag(free.astype(float))
+        # active-set corrections: add violated rows, drop wrong-sign ones.  The first ten passes drop every
+        # wrong-sign row at once; where that cycles (the exp weights' nearly flat directions) the later passes
+        # drop ONE, the most negative, as a primal active-set method does
+        for _outer in range(10 + 4 * N):
             zp = z.copy()
-            for _ in range(6):
+            for _ in range(6 + 2 * N):  # (the exp weights hand a violated bound on to the next stage, one per round)
                 Ga = G[act]
                 for _ in range(20):
                     g = self._grad(zp)
@@ -225,7 +234,10 @@ class BiMPCLiteral:
                     try:
                         sol = np.linalg.solve(K, rhs)
                     except np.linalg.LinAlgError:
-                        sol = np.linalg.lstsq(K, rhs, rcond=1e-14)[0]
+                        try:
+                            sol = np.linalg.lstsq(K, rhs, rcond=1e-14)[0]
+                        except np.linalg.LinAlgError:  # (the SVD did not converge)
+                            return None
                     dz, nu = sol[:n], sol[n:]
                     zp = zp + dz
                     if np.max(np.abs(dz)) <= 1e-15:
@@ -240,6 +252,8 @@ class BiMPCLiteral:
             neg = nu < -1e-9 * (1 + np.max(np.abs(g)))
             if not np.any(neg):
                 break
+            if _outer >= 10:
+                neg = np.arange(len(nu)) == np.argmin(nu)
             act = act[~neg]
         else:
             return None

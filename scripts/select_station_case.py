@@ -20,6 +20,14 @@ steps' partitions hold fewer EVs); the selected cases run two:
     python scripts/select_station_case.py 16 16 2     # M_2 768, seed 6
 
     python scripts/select_station_case.py [n_lo n_bi [Tf]]
+
+The small cases with another BiMPC charging cost or price type (M_2 = 60, the example's horizons) take the
+first seed of 1..8 that meets the last two state rules alone — every tested average error at least
+1e-6 tol away from tol, and a re-draw or a partition move (at five EVs per partition the piece share says
+nothing):
+
+    python scripts/select_station_case.py 12 16 2 --small --cost WEIGHTED          # seed 1
+    python scripts/select_station_case.py 12 16 2 --small --price-type linear      # seed 1
 """
 import os
 import sys
@@ -52,11 +60,12 @@ def patterns(ps, lm):
     return len(np.unique(code, axis=0))
 
 
-def trajectory(n_lo, n_bi, M_2, seed, Tf):
+def trajectory(n_lo, n_bi, M_2, seed, Tf, cost="UNWEIGHTED", price_type="linear-convex"):
     c = T.consts(M_2, Tf=Tf, n_lo=n_lo, n_bi=n_bi)
     np.random.seed(seed)
-    bi = dict(delta=1e3, c_g=1, u_g_max=1, u_b_max=0.3, x_max=0.3, cost_type=1, exp_rate=5)
-    so = SO.OracleStation(n_bi, n_lo, M_2, T.P, c.demand, bi, O.small_consts(), O.large_consts(), "linear-convex", Tf)
+    bi = dict(delta=1e3, c_g=1, u_g_max=1, u_b_max=0.3, x_max=0.3, cost_type=T.BiMPCChargingCostType[cost].value,
+              exp_rate=5)
+    so = SO.OracleStation(n_bi, n_lo, M_2, T.P, c.demand, bi, O.small_consts(), O.large_consts(), price_type, Tf)
     loops, margin = [], [np.inf]
     for ps in (so.ps_s, so.ps_l):
         ps.warm = "state"
@@ -92,13 +101,26 @@ def trajectory(n_lo, n_bi, M_2, seed, Tf):
 
 
 def main(argv):
+    opts = {}
+    for flag in ("--cost", "--price-type"):
+        if flag in argv:
+            i = argv.index(flag)
+            opts[flag] = argv[i + 1]
+            del argv[i: i + 2]
+    small = "--small" in argv
+    argv = [a for a in argv if a != "--small"]
     n_lo, n_bi = (int(argv[0]), int(argv[1])) if len(argv) >= 2 else (12, 16)
     Tf = int(argv[2]) if len(argv) >= 3 else T.TF
-    for M_2 in SIZES:
+    cost, price_type = opts.get("--cost", "UNWEIGHTED"), opts.get("--price-type", "linear-convex")
+    for M_2 in (60,) if small else SIZES:
         for seed in SEEDS:
-            r = trajectory(n_lo, n_bi, M_2, seed, Tf)
-            ok = r["share"] >= 0.5 and r["moved"].min() >= 1 and r["ncharged"] > 0 and r["margin"] >= EDGE
-            print(f"n_lo {n_lo} n_bi {n_bi} Tf {Tf} M_2 {M_2} seed {seed}: loops {r['loops']}  >=2-pattern share "
+            r = trajectory(n_lo, n_bi, M_2, seed, Tf, cost, price_type)
+            if small:
+                ok = r["margin"] >= EDGE and (r["ncharged"] > 0 or r["moved"].max() >= 1)
+            else:
+                ok = r["share"] >= 0.5 and r["moved"].min() >= 1 and r["ncharged"] > 0 and r["margin"] >= EDGE
+            print(f"{cost} {price_type} " * small +
+                  f"n_lo {n_lo} n_bi {n_bi} Tf {Tf} M_2 {M_2} seed {seed}: loops {r['loops']}  >=2-pattern share "
                   f"{r['share']:.3f}  moved s/l {r['moved'][0]}/{r['moved'][1]}  ncharged {r['ncharged']}  "
                   f"closest |err - tol| / tol {r['margin']:.3e}  max niter {r['niter_max']}  oracle {r['seconds']:.2f} s  "
                   f"{'SELECTED' if ok else 'no'}", flush=True)

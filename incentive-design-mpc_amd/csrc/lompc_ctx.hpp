@@ -177,7 +177,9 @@ struct lompc_plan {
   struct lq_host_loop* h_loop = nullptr;  // pinned: progress / done / results, written by k_loop_step
   double* h_dec = nullptr;        // pinned [2][max_iter]: dual cost decreases (actual, predicted)
   int cap_loop_iter = 0;
-  double* d_aggrec = nullptr;     // [S * G][LQ_AGG_REC] k_loop_iter's cell records
+  char* h_jobs = nullptr;         // pinned: the loops' records of a k_loop_runs launch this plan leads
+  int64_t cap_jobs = 0;           // its capacity in records
+  double* d_aggrec = nullptr;    // [S * G][LQ_AGG_REC] k_loop_iter's cell records
   int64_t cap_aggrec = 0;
   int64_t aggrec_zero = -1;       // offset of its zeroed padding record (-1: none yet)
   // gamma-sorted sets (LOMPC_PLAN_SORTED_GAMMA, lompc_agg.hpp): runs without per-EV outputs
@@ -268,5 +270,14 @@ int lq_launch_loop_run(lompc_plan* p, const double* lmbd, const double* lmbd_r, 
                        const StepArgs& sa, hipStream_t st);
 int lq_launch_loop(lompc_plan* p, const double* lmbd, const double* lmbd_r, double* set_sum_w, double* set_stats,
                    const StepArgs& sa, int m, hipStream_t st, bool persistent);
+// L independent persistent loops as one launch (k_loop_runs, lompc_plan.hip): whether the plan's loop can
+// join one, the size of a loop's record, the record of one loop (host memory the device can read), the
+// kernel's resident one-wave workgroups on the plan's device, and the launch
+bool lq_loop_runs_ok(const lompc_plan* p);
+size_t lq_loop_job_bytes();
+int lq_loop_job_fill(lompc_plan* p, const double* dev_in, double* set_sum_w, double* set_stats, const StepArgs& sa,
+                     void* slot, hipStream_t st);
+int lq_loop_runs_places(lompc_plan* p, int* places);
+int lq_launch_loop_runs(lompc_plan* p, int n_jobs, const void* d_jobs, hipStream_t st);
 int lq_price_loop_host(lompc_plan* p, const lompc_price_loop_args* a, double* lmbd, double* w_k, double* dual_cost,
                        double* dec_actual, double* dec_pred, int* iterations, double* errs, hipStream_t st);

@@ -17,6 +17,9 @@
 // Fused form (gamma-sorted sets, one rank, <= LQ_LOOP_G cells per set): the engine call and the
 // step are ONE launch, k_loop_iter (lompc_plan.hip) — path, aggregation and step without the two
 // kernel boundaries between them.
+// Batched form (lompc_price_loops): L independent loops in one call; those the persistent form takes
+// share persistent launches (k_loop_runs, lompc_plan.hip), each loop on its own plan's counter, records,
+// loop state and pinned results, the others run through lompc_price_loop one at a time.
 #include <hip/hip_runtime.h>
 #include <string.h>
 
@@ -44,14 +47,24 @@ double now_us() {
   return std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now().time_since_epoch()).count();
 }
 
-}  // namespace
+// A_bar = A'A + kappa I, the metric the device forms compute themselves
+bool standard_metric(const lompc_price_loop_args* a) {
+  const int N = a->N;
+  double worst = 0.0;
+  for (int i = 0; i < N; ++i)
+    for (int j = 0; j < N; ++j) {
+      const double ref = (double)(N - std::max(i, j)) + (i == j ? a->kappa : 0.0);
+      worst = std::max(worst, std::fabs(a->A_bar[(size_t)i * N + j] - ref));
+    }
+  return worst <= 1e-12 * (1.0 + N + a->kappa);
+}
 
-int lq_price_loop_device(lompc_plan* p, const lompc_price_loop_args* a, double* lmbd, double* w_k, double* dual_cost,
-                         double* dec_actual, double* dec_pred, int* iterations, double* errs, hipStream_t st) {
+// The start of a device loop on the plan: its buffers (allocated at the plan's first loop, the decrease
+// rows when the cap grows), the first prices staged and copied as in the host loop, the loop state zeroed
+// on the stream (after any call of the previous loop still in flight, which skips), the pinned block
+// reset; sa: the loop's step arguments
+int loop_begin(lompc_plan* p, const lompc_price_loop_args* a, const double* lmbd, hipStream_t st, StepArgs& sa) {
   const int N = a->N, N3 = 3 * N, MI = a->max_iter;
-  double* prof = a->prof;
-  const double t_start = prof ? now_us() : 0.0;
-  double t_issue = 0.0, t_wait = 0.0;
   int rc;
   if (!p->d_loop && (rc = grow(p, reinterpret_cast<char**>(&p->d_loop), LQ_LOOP_BYTES))) return rc;
   if (!p->h_loop)
@@ -67,8 +80,6 @@ int lq_price_loop_device(lompc_plan* p, const lompc_price_loop_args* a, double* 
   HIPCHK(p, hipHostGetDevicePointer((void**)&d_h, p->h_loop, 0));
   HIPCHK(p, hipHostGetDevicePointer((void**)&d_dec, p->h_dec, 0));
   volatile lq_host_loop* h = p->h_loop;
-  // the first prices: staged and copied as in the host loop; the loop state zeroed on the stream
-  // (after any call of the previous loop still in flight, which skips)
   double* hin = a->host_in;
   memcpy(hin, lmbd, N3 * sizeof(double));
   memcpy(hin + N3, lmbd, N3 * sizeof(double));
@@ -82,10 +93,55 @@ int lq_price_loop_device(lompc_plan* p, const lompc_price_loop_args* a, double* 
   h->done = 0;
   h->err = 0;
   h->conv_at = -1;
-  StepArgs sa{N,        a->r,        MI,       a->tol_avg, a->theta, a->w_max, a->m,
-              a->kappa, a->eps_reg,  a->tol,   a->n_evs,   a->dev_sw, a->dev_st, a->dev_in,
-              p->d_loop, reinterpret_cast<double*>(reinterpret_cast<char*>(p->d_loop) + 16),
-              reinterpret_cast<double*>(reinterpret_cast<char*>(p->d_loop) + LQ_LOOP_TRI), d_h, d_dec};
+  sa = StepArgs{N,        a->r,        MI,       a->tol_avg, a->theta, a->w_max, a->m,
+                a->kappa, a->eps_reg,  a->tol,   a->n_evs,   a->dev_sw, a->dev_st, a->dev_in,
+                p->d_loop, reinterpret_cast<double*>(reinterpret_cast<char*>(p->d_loop) + 16),
+                reinterpret_cast<double*>(reinterpret_cast<char*>(p->d_loop) + LQ_LOOP_TRI), d_h, d_dec};
+  return LOMPC_OK;
+}
+
+// The end of a finished device loop (the pinned block's `done` seen): its error, or its outputs
+int loop_result(lompc_plan* p, const lompc_price_loop_args* a, double* lmbd, double* w_k, double* dual_cost,
+                double* dec_actual, double* dec_pred, int* iterations, double* errs, hipStream_t st) {
+  const int N = a->N, N3 = 3 * N, MI = a->max_iter;
+  volatile lq_host_loop* h = p->h_loop;
+  const long long err = h->err;
+  const int it = (int)h->conv_at;
+  if (err == 1) return fail_arg(p, "gamma outside [0, y_max]");
+  if (err == 2) {
+    p->err = lq_failed_text(p, st);
+    return LOMPC_ERR_NOT_CONVERGED;
+  }
+  if (err == 3) {
+    p->err = "price-gradient QP: no certified optimum";
+    return LOMPC_ERR_NOT_CONVERGED;
+  }
+  *iterations = it;
+  for (int i = 0; i < N3; ++i) lmbd[i] = h->lmbd[i];
+  for (int i = 0; i < N; ++i) w_k[i] = h->w_k[i];
+  if (dual_cost) *dual_cost = h->dual_cost;
+  if (errs)
+    for (int k = 0; k < 3; ++k) errs[k] = h->errs[k];
+  const volatile double* hd = p->h_dec;
+  for (int i = 0; i < it; ++i) {
+    if (dec_actual) dec_actual[i] = hd[i];
+    if (dec_pred) dec_pred[i] = hd[MI + i];
+  }
+  return LOMPC_OK;
+}
+
+}  // namespace
+
+int lq_price_loop_device(lompc_plan* p, const lompc_price_loop_args* a, double* lmbd, double* w_k, double* dual_cost,
+                         double* dec_actual, double* dec_pred, int* iterations, double* errs, hipStream_t st) {
+  const int N = a->N, N3 = 3 * N, MI = a->max_iter;
+  double* prof = a->prof;
+  const double t_start = prof ? now_us() : 0.0;
+  double t_issue = 0.0, t_wait = 0.0;
+  int rc;
+  StepArgs sa;
+  if ((rc = loop_begin(p, a, lmbd, st, sa))) return rc;
+  volatile lq_host_loop* h = p->h_loop;
   const int ahead = LOMPC_LOOP_AHEAD;
   const bool fused = lq_loop_fusable(p, LQ_LOOP_PERSIST);
   auto done = [&]() { return __atomic_load_n(const_cast<long long*>(&h->done), __ATOMIC_ACQUIRE) != 0; };
@@ -153,7 +209,6 @@ int lq_price_loop_device(lompc_plan* p, const lompc_price_loop_args* a, double* 
   if (rc) return rc;
   if ((rc = wait_for(done))) return rc;
   }
-  const long long err = h->err;
   const int it = (int)h->conv_at;
   if (prof) {
     prof[LOMPC_LOOP_PROF_ITERS] += it + 1;
@@ -165,27 +220,7 @@ int lq_price_loop_device(lompc_plan* p, const lompc_price_loop_args* a, double* 
     prof[LOMPC_LOOP_PROF_HOST] = prof[LOMPC_LOOP_PROF_WALL] - prof[LOMPC_LOOP_PROF_ISSUE] -
                                  prof[LOMPC_LOOP_PROF_WAIT] - prof[LOMPC_LOOP_PROF_STEP];
   }
-  if (err == 1) return fail_arg(p, "gamma outside [0, y_max]");
-  if (err == 2) {
-    p->err = lq_failed_text(p, st);
-    return LOMPC_ERR_NOT_CONVERGED;
-  }
-  if (err == 3) {
-    p->err = "price-gradient QP: no certified optimum";
-    return LOMPC_ERR_NOT_CONVERGED;
-  }
-  *iterations = it;
-  for (int i = 0; i < N3; ++i) lmbd[i] = h->lmbd[i];
-  for (int i = 0; i < N; ++i) w_k[i] = h->w_k[i];
-  if (dual_cost) *dual_cost = h->dual_cost;
-  if (errs)
-    for (int k = 0; k < 3; ++k) errs[k] = h->errs[k];
-  const volatile double* hd = p->h_dec;
-  for (int i = 0; i < it; ++i) {
-    if (dec_actual) dec_actual[i] = hd[i];
-    if (dec_pred) dec_pred[i] = hd[MI + i];
-  }
-  return LOMPC_OK;
+  return loop_result(p, a, lmbd, w_k, dual_cost, dec_actual, dec_pred, iterations, errs, st);
 }
 
 extern "C" {
@@ -199,16 +234,8 @@ int lompc_price_loop(lompc_plan* p, const lompc_price_loop_args* a, double* lmbd
   if (N != p->N || p->S != 2 || (r != 2 * N && r != 3 * N)) return fail_arg(p, "price loop: a plan of 2 sets of horizon N");
   HIPCHK(p, hipSetDevice(p->device));
   hipStream_t st = (hipStream_t)stream;
-  bool dev = a->device_loop != 0;
-  if (dev) {  // the device form computes the metric as A'A + kappa I: check that A_bar is that
-    double worst = 0.0;
-    for (int i = 0; i < N; ++i)
-      for (int j = 0; j < N; ++j) {
-        const double ref = (double)(N - std::max(i, j)) + (i == j ? a->kappa : 0.0);
-        worst = std::max(worst, std::fabs(a->A_bar[(size_t)i * N + j] - ref));
-      }
-    dev = worst <= 1e-12 * (1.0 + N + a->kappa);
-  }
+  // the device form computes the metric as A'A + kappa I: check that A_bar is that
+  const bool dev = a->device_loop != 0 && standard_metric(a);
   if (dev) return lq_price_loop_device(p, a, lmbd, w_k, dual_cost, dec_actual, dec_pred, iterations, errs, st);
   return lq_price_loop_host(p, a, lmbd, w_k, dual_cost, dec_actual, dec_pred, iterations, errs, st);
 }
@@ -287,6 +314,180 @@ int lompc_price_chain(int n_parts, lompc_price_chain_part* parts, const lompc_pr
     if (q.rc) return q.rc;
     for (int i = 0; i < r; ++i) prev_prices[i] = lm[i];
   }
+  return LOMPC_OK;
+}
+
+// L independent price loops, those the persistent form takes as shared k_loop_runs launches
+// (include/lompc_amd.h)
+int lompc_price_loops(int n_parts, lompc_price_loops_part* parts, int max_parts_per_launch, int* launches,
+                      void* stream) {
+  if (n_parts < 0 || (n_parts > 0 && !parts)) return LOMPC_ERR_INVALID_ARG;
+  // refusals: before anything is launched or written
+  for (int k = 0; k < n_parts; ++k) {
+    const lompc_price_loops_part& q = parts[k];
+    const lompc_price_loop_args* a = q.args;
+    if (!q.plan || !a || !q.lmbd || !q.w_k || !a->A_bar || !a->w_ref || !a->dev_in || !a->host_in || !a->dev_sw ||
+        !a->dev_st || !a->host_sw || !a->host_st || a->N < 1 || a->N > LOMPC_MAX_N)
+      return LOMPC_ERR_INVALID_ARG;
+    if (q.plan->device != parts[0].plan->device) return LOMPC_ERR_INVALID_ARG;
+    const size_t n_in = 8 * (size_t)a->N + 2;
+    for (int j = 0; j < k; ++j) {
+      const lompc_price_loop_args* b = parts[j].args;
+      const size_t m_in = 8 * (size_t)b->N + 2;
+      if (parts[j].plan == q.plan) return LOMPC_ERR_INVALID_ARG;
+      if ((a->dev_in < b->dev_in + m_in && b->dev_in < a->dev_in + n_in) ||
+          (a->host_in < b->host_in + m_in && b->host_in < a->host_in + n_in))
+        return LOMPC_ERR_INVALID_ARG;
+    }
+  }
+  if (launches) *launches = 0;
+  if (n_parts == 0) return LOMPC_OK;
+  hipStream_t st = (hipStream_t)stream;
+  lompc_plan* p0 = parts[0].plan;
+  HIPCHK(p0, hipSetDevice(p0->device));
+  // the loop's start prices (regularize: the chain's, prices past r dropped) and the ends of a part
+  auto start_of = [](const lompc_price_loops_part& q, std::vector<double>& lm) {
+    const int N3 = 3 * q.args->N;
+    lm.assign(q.lmbd, q.lmbd + N3);
+    if (q.regularize)
+      for (int i = q.args->r; i < N3; ++i) lm[i] = 0.0;
+  };
+  auto finish = [](lompc_price_loops_part& q, int it) {
+    const lompc_price_loop_args* a = q.args;
+    q.calls = it + 1;
+    q.iterations = it;
+    if (!q.regularize) return;
+    q.iterations = std::min(it, a->max_iter - 1);  // (the reference's loop variable at its end)
+    q.rc = lompc_price_regularize(a->N, a->r, a->theta, a->w_max, q.w_k, q.lmbd, &q.price_before_reg,
+                                  &q.price_after_reg);
+  };
+  std::vector<char> batched(n_parts, 0), seen(n_parts, 0);
+  for (int k = 0; k < n_parts; ++k) {
+    lompc_price_loops_part& q = parts[k];
+    const lompc_price_loop_args* a = q.args;
+    q.rc = LOMPC_OK;
+    batched[k] = LQ_LOOP_PERSIST && a->device_loop != 0 && a->max_iter >= 1 && a->n_evs > 0.0 && a->N == q.plan->N &&
+                 (a->r == 2 * a->N || a->r == 3 * a->N) && lq_loop_runs_ok(q.plan) && standard_metric(a);
+  }
+  std::vector<double> lm;
+  // the parts the persistent form takes: those of one (N, r, cell count) share launches, in part order
+  for (int k0 = 0; k0 < n_parts; ++k0) {
+    if (!batched[k0] || seen[k0]) continue;
+    lompc_plan* lead = parts[k0].plan;
+    std::vector<int> grp;
+    for (int k = k0; k < n_parts; ++k)
+      if (batched[k] && !seen[k] && parts[k].args->N == parts[k0].args->N && parts[k].args->r == parts[k0].args->r &&
+          parts[k].plan->G == lead->G) {
+        grp.push_back(k);
+        seen[k] = 1;
+      }
+    // at most half of the kernel's resident places per launch (other streams' kernels may hold places)
+    int places = 0;
+    if (lq_loop_runs_places(lead, &places)) places = 0;
+    int cap = places / 2 / (2 * lead->G);
+    if (max_parts_per_launch > 0) cap = std::min(cap, max_parts_per_launch);
+    if (cap < 1) {  // (no room for one loop beside others: the single loop's own launch)
+      for (int k : grp) batched[k] = 0;
+      continue;
+    }
+    const size_t jb = lq_loop_job_bytes();
+    for (size_t g0 = 0; g0 < grp.size(); g0 += (size_t)cap) {
+      const int n = (int)std::min(grp.size() - g0, (size_t)cap);
+      lead = parts[grp[g0]].plan;
+      if (n > lead->cap_jobs) {
+        if (lead->h_jobs) HIPCHK(lead, hipHostFree(lead->h_jobs));
+        lead->h_jobs = nullptr;
+        lead->cap_jobs = 0;
+        HIPCHK(lead, hipHostMalloc((void**)&lead->h_jobs, (size_t)n * jb, hipHostMallocCoherent | hipHostMallocMapped));
+        lead->cap_jobs = n;
+      }
+      std::vector<int> live;
+      for (int i = 0; i < n; ++i) {
+        lompc_price_loops_part& q = parts[grp[g0 + i]];
+        const lompc_price_loop_args* a = q.args;
+        lompc_plan* p = q.plan;
+        StepArgs sa;
+        start_of(q, lm);
+        if ((q.rc = loop_begin(p, a, lm.data(), st, sa))) continue;
+        p->skip = p->d_loop;
+        q.rc = lq_loop_job_fill(p, a->dev_in, const_cast<double*>(a->dev_sw), const_cast<double*>(a->dev_st), sa,
+                                lead->h_jobs + live.size() * jb, st);
+        p->skip = nullptr;
+        if (!q.rc) live.push_back(grp[g0 + i]);
+      }
+      if (live.empty()) continue;
+      void* d_jobs = nullptr;
+      int rc = LOMPC_OK;
+      if (hipHostGetDevicePointer(&d_jobs, lead->h_jobs, 0) != hipSuccess) {
+        lead->err = "hipHostGetDevicePointer: the loops' records";
+        rc = LOMPC_ERR_HIP;
+      }
+      if (!rc) rc = lq_launch_loop_runs(lead, (int)live.size(), d_jobs, st);
+      if (rc) {
+        for (int k : live) {
+          parts[k].rc = rc;
+          if (parts[k].plan != lead) parts[k].plan->err = lead->err;
+        }
+        continue;
+      }
+      if (launches) ++*launches;
+      // every loop's `done` — or the launch over without it (a wave's bounded spin expired: ctl[3])
+      auto done = [&](int k) {
+        return __atomic_load_n(const_cast<long long*>(&parts[k].plan->h_loop->done), __ATOMIC_ACQUIRE) != 0;
+      };
+      auto all_done = [&]() {
+        for (int k : live)
+          if (!done(k)) return false;
+        return true;
+      };
+      const double t0 = now_us();
+      bool stuck = false;
+      while (!all_done()) {
+        if (hipStreamQuery(st) == hipSuccess) break;  // (the launch is over: `done` was set before it ended, or never)
+        __builtin_ia32_pause();
+        if (now_us() - t0 > 20e6) {
+          stuck = true;
+          break;
+        }
+      }
+      for (int k : live) {
+        lompc_price_loops_part& q = parts[k];
+        if (!done(k)) {
+          q.plan->err = stuck ? "device price loop: no progress for 20 s"
+                              : "device price loop: a persistent wave timed out waiting for the next call";
+          q.rc = LOMPC_ERR_HIP;
+          continue;
+        }
+        int it = 0;
+        q.rc = loop_result(q.plan, q.args, q.lmbd, q.w_k, &q.dual_cost, q.dec_actual, q.dec_pred, &it, q.errs, st);
+        if (!q.rc) finish(q, it);
+      }
+      if (stuck) break;  // (the stream still holds the launch: nothing more behind it)
+    }
+  }
+  // every other part: the single loop, one at a time, its reference w read from its own price buffer too
+  for (int k = 0; k < n_parts; ++k) {
+    if (batched[k]) continue;
+    lompc_price_loops_part& q = parts[k];
+    const lompc_price_loop_args* a = q.args;
+    lompc_plan* p = q.plan;
+    start_of(q, lm);
+    std::vector<double> wk(a->N);
+    int it = 0;
+    double dual = 0.0, errs[3] = {0.0, 0.0, 0.0};
+    const double* w_ref_plan = p->w_ref;
+    p->w_ref = a->dev_in + 6 * a->N + 2;
+    q.rc = lompc_price_loop(p, a, lm.data(), wk.data(), &dual, q.dec_actual, q.dec_pred, &it, errs, stream);
+    p->w_ref = w_ref_plan;
+    if (q.rc) continue;
+    memcpy(q.lmbd, lm.data(), lm.size() * sizeof(double));
+    memcpy(q.w_k, wk.data(), wk.size() * sizeof(double));
+    q.dual_cost = dual;
+    memcpy(q.errs, errs, sizeof(errs));
+    finish(q, it);
+  }
+  for (int k = 0; k < n_parts; ++k)
+    if (parts[k].rc) return parts[k].rc;
   return LOMPC_OK;
 }
 

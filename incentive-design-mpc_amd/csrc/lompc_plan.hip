@@ -2412,6 +2412,7 @@ __global__ __launch_bounds__(64) void k_loop_run(PathArgs pa, AggArgs ga, StepAr
 // records alternate between two buffers by call parity (a wave may write call m + 1's record while a
 // slower wave still reads call m's: never call m + 2's, which needs every wave's call m + 1 arrival).
 // The same arithmetic as k_loop_run and k_loop_iter: the same bits.
+// The body is the text of lompc_looprun2_body.hpp, which k_loop_runs (below) includes too.
 #ifndef LQ_LOOP_REDUNDANT
 #define LQ_LOOP_REDUNDANT 1
 #endif
@@ -2419,132 +2420,46 @@ template <int NT>
 __global__ __launch_bounds__(64) void k_loop_run2(PathArgs pa, AggArgs ga, StepArgs sa, double* rec) {
   constexpr int S = 2;
   const int blk = (int)blockIdx.x, lane = (int)threadIdx.x, G = pa.G;
-  const int s = blk / G, c = blk - s * G;
-  const bool writer = blk == 0;
-  int cl_n[S], cl_v[S], cl_ok[S];
+#include "lompc_looprun2_body.hpp"
+}
+
+// ---------------------------------------------------------------- k_loop_runs
+// L independent price loops in ONE persistent launch (lompc_price_loops): L * S * G one-wave
+// workgroups, workgroup b the wave blk = b - j * S * G of loop j = b / (S * G).  The wave takes loop j's
+// record — what k_loop_run2 gets as kernel arguments — from the job array (wave-uniform scalar loads
+// from constant memory, as kernel arguments are) and runs k_loop_run2's body on it
+// (lompc_looprun2_body.hpp).  No object is shared between loops: each record names its own plan's arrival counter, cell records, zero record, loop state,
+// pinned results and price buffer, so a loop's waves wait for that loop's S * G arrivals alone, and a
+// loop that ends (converged, capped, failed, expired spin) leaves while the others go on.  The host
+// launches no more loops than are resident at once (lq_loop_runs_places).
+struct LoopJob {
+  PathArgs pa;
+  AggArgs ga;
+  StepArgs sa;
+  double* rec;
+};
+static_assert(sizeof(LoopJob) % 4 == 0, "LoopJob is copied by words");
+
+template <int NT>
+__global__ __launch_bounds__(64) void k_loop_runs(const LoopJob* jobs, int waves) {
+  // (waves = S * G of every loop of the launch; the quotient comes out of the vector ALU: made scalar again)
+  const int b = (int)blockIdx.x, j = __builtin_amdgcn_readfirstlane(b / waves);
+  typedef const __attribute__((address_space(4))) unsigned int* cwords;
+  cwords src = (cwords)(reinterpret_cast<const unsigned int*>(jobs + j));
+  union U {
+    LoopJob job;
+    unsigned int w[sizeof(LoopJob) / 4];
+    __device__ U() {}
+  } u;
 #pragma unroll
-  for (int t = 0; t < S; ++t) {
-    const int4 si = ga.sinfo[t];
-    cl_n[t] = (int)(ga.set_off[t + 1] - ga.set_off[t]);
-    cl_v[t] = si.x;
-    cl_ok[t] = si.y;
-    asm volatile("" : "+v"(cl_n[t]), "+v"(cl_v[t]), "+v"(cl_ok[t]));
-  }
-  AggArgs gw = ga;  // (the closing's outputs: wave 0's only)
-  if (!writer) {
-    gw.set_sum_w = nullptr;
-    gw.set_stats = nullptr;
-    gw.stats = nullptr;
-    gw.tally = nullptr;
-  }
-  const int nsg = S * G;
-  StepIn in;
-  step_prices<false>(sa, lane, in);  // (the first call's prices, w_ref, the zeroed loop state)
-  double pv[3] = {in.lm[0], in.lm[1], in.lm[2]};
-  // the cell's stored working set, kept in a register from call to call (as each call stores it);
-  // w_ref from the price buffer (the plan's w_ref of both sets, constant over the loop)
-  const int N_ = NT ? NT : pa.N;
-  const double wr_c = (pa.w_ref && lane < N_) ? pa.w_ref[(size_t)s * N_ + lane] : 0.0;
-  int wsr = pa.ws ? (int)pa.ws[(size_t)blk * 64 + lane] : 0;
-  for (int m = 0; m <= sa.max_iter; ++m) {
-    // (the box table in LDS: written by the first call; the one-wave workgroup keeps its LDS)
-    if (m == 0) path_cell<NT, true, true, true>(pa, blk, pv[0], pv[1], pv[2], wr_c, &wsr);
-    else path_cell<NT, false, true, true>(pa, blk, pv[0], pv[1], pv[2], wr_c, &wsr);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the cell's tables have reached L2
-    double* rb = rec + (size_t)(m & 1) * (nsg + 1) * LQ_AGG_REC;  // this call's record buffer
-    {
-      AggSet z = agg_set_init<NT, true>(ga, s);
-      if (m > 0) {  // (the prices of this call: registers)
-        z.preg = true;
-        z.p1 = pv[0];
-        z.p2 = pv[1];
-        z.p3 = pv[2];
-        z.l1 = lqw::readlane_d(pv[0], 0);
-        z.l2 = lqw::readlane_d(pv[1], 0);
-        z.l3 = lqw::readlane_d(pv[2], 0);
-      }
-      AggPart ap;
-      if (z.order_ok) agg_cell<NT, true, true>(ga, z, s, c, agg_cell_range(z, c), lane, ap);
-      const AggRec x = agg_wave_record(ap);
-      double* rc = rb + (size_t)blk * LQ_AGG_REC;
-      if (lane < z.N) st_wt8(rc + lane, ap.accw);
-      if (lane < 5) st_wt8(rc + LOMPC_MAX_N + lane, x.pick(lane));
-    }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    int ok = 1;
-    if (lane == 0) {
-      __hip_atomic_fetch_add(sa.ctl + 1, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      const int target = (m + 1) * nsg;
-      int spins = 0;
-      while (__hip_atomic_load(sa.ctl + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < target) {
-        __builtin_amdgcn_s_sleep(1);
-        if (++spins >= LQ_RUN_SPINS) {
-          ok = 0;
-          break;
-        }
-      }
-      if (!ok) {
-        __hip_atomic_store(sa.ctl + 3, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        __hip_atomic_store(sa.ctl + 0, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      }
-    }
-    if (!lqw::readlane_i(ok, 0)) return;
-    AggSet zs[S];
-#pragma unroll
-    for (int t = 0; t < S; ++t) {
-      zs[t].N = NT ? NT : ga.N;
-      zs[t].n_s = cl_n[t];
-      zs[t].si = make_int4(cl_v[t], cl_ok[t], 0, 0);
-      zs[t].order_ok = cl_ok[t] != 0;
-    }
-    const int N = zs[0].N;
-    const int tl = min(lane, N - 1), xl = min(lane, 4);
-    // the records in cell order, 16 of each set per memory round (records k >= G: the zero record
-    // after buffer 0; with G <= 16 one round, the sums of k_loop_run's padded 16)
-    double v[S] = {0.0, 0.0}, xs[S] = {0.0, 0.0}, xm[S] = {0.0, 0.0};
-    for (int k0 = 0; k0 < G; k0 += LQ_LOOP_G) {  // (wave-uniform)
-      double rw[S][LQ_LOOP_G], rx[S][LQ_LOOP_G];
-#pragma unroll
-      for (int t = 0; t < S; ++t)
-#pragma unroll
-        for (int k = 0; k < LQ_LOOP_G; ++k) {
-          const double* rk =
-              k0 + k < G ? rb + (size_t)(t * G + k0 + k) * LQ_AGG_REC : rec + (size_t)nsg * LQ_AGG_REC;
-          rw[t][k] = ld_t<true>(rk + tl);
-          rx[t][k] = ld_t<true>(rk + LOMPC_MAX_N + xl);
-        }
-#pragma unroll
-      for (int t = 0; t < S; ++t)
-#pragma unroll
-        for (int k = 0; k < LQ_LOOP_G; ++k) {
-          v[t] += rw[t][k];
-          xs[t] += rx[t][k];
-          xm[t] = fmax(xm[t], rx[t][k]);
-        }
-    }
-    AggSetOut o[S];
-#pragma unroll
-    for (int t = 0; t < S; ++t) o[t] = agg_finish_tail<false>(gw, zs[t], t, lane, v[t], xs[t], xm[t]);
-    in.s0 = o[0].sumw;
-    in.wk = o[1].sumw;
-    in.emax = lqw::readlane_d(o[0].stat, LOMPC_STAT_MAX_ERR);
-    in.cost_c = lqw::readlane_d(o[1].stat, LOMPC_STAT_SUM_COST);
-    in.n_inv = lqw::readlane_d(o[0].stat, LOMPC_STAT_N_INVALID) + lqw::readlane_d(o[1].stat, LOMPC_STAT_N_INVALID);
-    in.n_fail = lqw::readlane_d(o[0].stat, LOMPC_STAT_N_FAILED) + lqw::readlane_d(o[1].stat, LOMPC_STAT_N_FAILED);
-    StepOut so;
-    if (writer) loop_step_core<NoStamp, NoRelease, true>(sa, m, lane, in, NoStamp{}, NoRelease{}, &so);
-    else loop_step_core<NoStamp, NoRelease, false>(sa, m, lane, in, NoStamp{}, NoRelease{}, &so);
-    if (so.fin) return;
-    // the next call's inputs: what the step stored, kept in registers
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-      pv[k] = so.v[k];
-      in.lm[k] = so.v[k];
-    }
-    in.dc = so.cost_c;
-    in.dterm = so.dterm;
-    in.ab = so.ab;
-  }
+  for (int k = 0; k < (int)(sizeof(LoopJob) / 4); ++k) u.w[k] = src[k];
+  const PathArgs& pa = u.job.pa;
+  const AggArgs& ga = u.job.ga;
+  const StepArgs& sa = u.job.sa;
+  double* const rec = u.job.rec;
+  constexpr int S = 2;
+  const int blk = b - j * waves, lane = (int)threadIdx.x, G = pa.G;
+#include "lompc_looprun2_body.hpp"
 }
 
 typedef void (*LoopRunKernel)(PathArgs, AggArgs, StepArgs, double*);
@@ -3332,24 +3247,14 @@ int lq_launch_loop_run(lompc_plan* p, const double* lmbd, const double* lmbd_r, 
   return lq_launch_loop(p, lmbd, lmbd_r, set_sum_w, set_stats, sa, 0, st, true);
 }
 
+int loop_records(lompc_plan* p, hipStream_t st);
+
 int lq_launch_loop(lompc_plan* p, const double* lmbd, const double* lmbd_r, double* set_sum_w, double* set_stats,
                    const StepArgs& sa, int m, hipStream_t st, bool persistent) {
   if (!lq_loop_fusable(p, persistent)) return fail_arg(p, "k_loop_iter: plan not fusable");
   const int N = p->N;
-  // [cell records | the zero record (k_loop_iter's padding) | (k_loop_run2) the second record buffer]
-  const int64_t zoff = p->S * p->G * (int64_t)LQ_AGG_REC;
-  const int64_t nrec = (2 * p->S * p->G + 1) * (int64_t)LQ_AGG_REC;
-  if (nrec > p->cap_aggrec) {
-    const int64_t c = std::max(nrec, p->reserve_B ? (2 * p->S * LQ_RESERVE_CELLS + 1) * (int64_t)LQ_AGG_REC : 0);
-    const int rc = grow(p, &p->d_aggrec, c);
-    if (rc) return rc;
-    p->cap_aggrec = c;
-    p->aggrec_zero = -1;
-  }
-  if (p->aggrec_zero != zoff) {  // (the cell records never reach it: zeroed once per layout)
-    HIPCHK(p, hipMemsetAsync(p->d_aggrec + zoff, 0, LQ_AGG_REC * sizeof(double), st));
-    p->aggrec_zero = zoff;
-  }
+  const int rr = loop_records(p, st);
+  if (rr) return rr;
   const PathTab tb = own_tab(p);
   const PathArgs pa = path_args(p, lmbd, lmbd_r, tb);
   AggArgs ga{(int)p->S, p->G, N, p->aggF, p->d_q, p->ce, p->d_set_off, p->d_window, p->gamma, lmbd, lmbd_r,
@@ -3365,6 +3270,80 @@ int lq_launch_loop(lompc_plan* p, const double* lmbd, const double* lmbd_r, doub
                           p->d_aggrec, m);
   HIPCHK(p, hipGetLastError());
   plan_prof_end(p, LOMPC_PLAN_K_PATH, e0, e1);
+  return LOMPC_OK;
+}
+
+// the plan's cell records, grown to its cell count, their zero record zeroed (on the stream)
+int loop_records(lompc_plan* p, hipStream_t st) {
+  // [cell records | the zero record (k_loop_iter's padding) | (k_loop_run2) the second record buffer]
+  const int64_t zoff = p->S * p->G * (int64_t)LQ_AGG_REC;
+  const int64_t nrec = (2 * p->S * p->G + 1) * (int64_t)LQ_AGG_REC;
+  if (nrec > p->cap_aggrec) {
+    const int64_t c = std::max(nrec, p->reserve_B ? (2 * p->S * LQ_RESERVE_CELLS + 1) * (int64_t)LQ_AGG_REC : 0);
+    const int rc = grow(p, &p->d_aggrec, c);
+    if (rc) return rc;
+    p->cap_aggrec = c;
+    p->aggrec_zero = -1;
+  }
+  if (p->aggrec_zero != zoff) {  // (the cell records never reach it: zeroed once per layout)
+    HIPCHK(p, hipMemsetAsync(p->d_aggrec + zoff, 0, LQ_AGG_REC * sizeof(double), st));
+    p->aggrec_zero = zoff;
+  }
+  return LOMPC_OK;
+}
+
+// ---- the batched persistent loops (lompc_price_loops, lompc_loop.hip; kernel k_loop_runs)
+bool lq_loop_runs_ok(const lompc_plan* p) { return LQ_LOOP_REDUNDANT && lq_loop_fusable(p, true); }
+
+size_t lq_loop_job_bytes() { return sizeof(LoopJob); }
+
+// loop j's record at ``slot`` (host): k_loop_run2's arguments for the plan with its price buffer dev_in
+// [2*3N | 2 | 2N] — the reference w of both sets read from THAT buffer, not from the pointer the plan
+// was created with (concurrent loops of one solver's partitions have different targets)
+int lq_loop_job_fill(lompc_plan* p, const double* dev_in, double* set_sum_w, double* set_stats, const StepArgs& sa,
+                     void* slot, hipStream_t st) {
+  if (!lq_loop_runs_ok(p)) return fail_arg(p, "k_loop_runs: plan not fusable");
+  const int rr = loop_records(p, st);
+  if (rr) return rr;
+  const int N = p->N;
+  const double *lmbd = dev_in, *lmbd_r = dev_in + 6 * N, *w_ref = dev_in + 6 * N + 2;
+  const PathTab tb = own_tab(p);
+  LoopJob job{path_args(p, lmbd, lmbd_r, tb),
+              AggArgs{(int)p->S, p->G, N, p->aggF, p->d_q, p->ce, p->d_set_off, p->d_window, p->gamma, lmbd, lmbd_r,
+                      w_ref, tb.cnt, tb.lo, tb.sl, tb.ge, tb.cf, tb.ab, p->d_P, p->B + p->S, p->d_pos,
+                      p->d_sinfo, set_sum_w, set_stats, p->d_stats, p->d_tally, p->skip},
+              sa, p->d_aggrec};
+  job.pa.w_ref = w_ref;
+  memcpy(slot, &job, sizeof(job));
+  return LOMPC_OK;
+}
+
+typedef void (*LoopRunsKernel)(const LoopJob*, int);
+LoopRunsKernel loop_runs_kernel(int N) {
+  switch (N) {
+    case 12: return k_loop_runs<12>;
+    case 16: return k_loop_runs<16>;
+    case 24: return k_loop_runs<24>;
+    case 48: return k_loop_runs<48>;
+    default: return k_loop_runs<0>;
+  }
+}
+
+// the one-wave workgroups of k_loop_runs<N> resident at once on the plan's device
+int lq_loop_runs_places(lompc_plan* p, int* places) {
+  int per_cu = 0, dev_cus = 0;
+  HIPCHK(p, hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void*)loop_runs_kernel(p->N), 64, 0));
+  HIPCHK(p, hipDeviceGetAttribute(&dev_cus, hipDeviceAttributeMultiprocessorCount, p->device));
+  *places = per_cu * dev_cus;
+  return LOMPC_OK;
+}
+
+// n_jobs loops of plans like p (same N and cell count), their records at d_jobs, as one launch
+int lq_launch_loop_runs(lompc_plan* p, int n_jobs, const void* d_jobs, hipStream_t st) {
+  const int nsg = (int)p->S * p->G;
+  hipLaunchKernelGGL(loop_runs_kernel(p->N), dim3((unsigned)(n_jobs * nsg)), dim3(64), 0, st,
+                     static_cast<const LoopJob*>(d_jobs), nsg);
+  HIPCHK(p, hipGetLastError());
   return LOMPC_OK;
 }
 
@@ -3394,6 +3373,7 @@ void lq_plan_free(lompc_plan* p) {
 
   if (p->h_loop) (void)hipHostFree(p->h_loop);
   if (p->h_dec) (void)hipHostFree(p->h_dec);
+  if (p->h_jobs) (void)hipHostFree(p->h_jobs);
   if (p->ev_stage) (void)hipEventDestroy(p->ev_stage);
   for (auto& v : p->prof_ev)
     for (hipEvent_t e : v) (void)hipEventDestroy(e);

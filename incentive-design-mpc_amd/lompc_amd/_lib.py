@@ -106,6 +106,7 @@ SIGNATURES = [
     ("lompc_plan_reserve", _I, [_P, _L]),
     ("lompc_price_loop", _I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     ("lompc_price_chain", _I, [_I, _P, _P, _P, _P]),
+    ("lompc_price_loops", _I, [_I, _P, _I, _P, _P]),
     ("lompc_plan_profile_enable", _I, [_P, _I]),
     ("lompc_plan_profile_read", _I, [_P, _I, _P, _P, _I]),
     ("lompc_plan_last_error", ctypes.c_char_p, [_P]),
@@ -153,6 +154,16 @@ class PriceChainPart(ctypes.Structure):
                 ("dec_pred", ctypes.c_void_p), ("iterations", ctypes.c_int), ("calls", ctypes.c_int),
                 ("rc", ctypes.c_int), ("pad", ctypes.c_int), ("price_before_reg", ctypes.c_double),
                 ("price_after_reg", ctypes.c_double)]
+
+
+class PriceLoopsPart(ctypes.Structure):
+    """include/lompc_amd.h lompc_price_loops_part."""
+    _fields_ = [("plan", ctypes.c_void_p), ("args", ctypes.c_void_p), ("lmbd", ctypes.c_void_p),
+                ("w_k", ctypes.c_void_p), ("dec_actual", ctypes.c_void_p), ("dec_pred", ctypes.c_void_p),
+                ("regularize", ctypes.c_int), ("iterations", ctypes.c_int), ("calls", ctypes.c_int),
+                ("rc", ctypes.c_int), ("pad", ctypes.c_int), ("dual_cost", ctypes.c_double),
+                ("price_before_reg", ctypes.c_double), ("price_after_reg", ctypes.c_double),
+                ("errs", ctypes.c_double * 3)]
 
 
 _lock = threading.Lock()

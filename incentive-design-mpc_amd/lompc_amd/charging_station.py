@@ -147,8 +147,20 @@ def redraw_full(y, mask, lo_val: float, hi_val: float, rng_random, group=None) -
 
 class ChargingStation:
     def __init__(self, consts: ChargingStationConstants, device: int | None = None, mode: str | None = None,
-                 group=None, sharded_loops: str = "replicated") -> None:
+                 group=None, sharded_loops: str = "replicated", price_start: str = "chained") -> None:
         # charging_station.py:44-53
+        if price_start not in ("chained", "own"):
+            raise ValueError("price_start: 'chained' or 'own'")
+        if price_start == "own" and group is not None:
+            raise ValueError("price_start='own': single process only (no process group)")
+        # "chained" (the reference's rule): within an EV type each partition's price loop starts from the
+        # previous partition's prices.  "own": every (type, partition) starts from ITS OWN previous prices
+        # (zeros at first), so a step's loops are independent and go out as one
+        # compute_optimal_prices_parallel call — another warm start, so another trajectory
+        self.price_start = price_start
+        # "own" only: False runs the same start rule one lompc_price_loop at a time (A/B: the same bits)
+        self.price_loops_batched = True
+        self._own_prev = {}  # "own": (kind, partition) -> that partition's previous prices (r,)
         assert consts.simulation_length >= 1
         assert (consts.horizon_bimpc >= consts.horizon_lompc) and (consts.horizon_lompc >= 1)
         assert consts.nEVs_per_EV_type >= 1
@@ -542,6 +554,8 @@ class ChargingStation:
         # GIL) on each solver's own stream.
         PRINT_LEVEL = _settings.PRINT_LEVEL
         self.chain_ms = {}
+        if self.price_start == "own":
+            return self._get_optimal_prices_own(w_hat_s, w_hat_l, lmbd_r)
         w_hat_s_opt, w_hat_l_opt = w_hat_s[:, : self.N_lo], w_hat_l[:, : self.N_lo]
         prices_s, prices_l = np.zeros((self.P, self.r)), np.zeros((self.P, self.r))
         stats_s, stats_l = [], []
@@ -640,6 +654,53 @@ class ChargingStation:
             for chain in chains:
                 main.wait_stream(chain[1]._stream)
         return prices_s, prices_l, stats_s, stats_l
+
+    def _get_optimal_prices_own(self, w_hat_s, w_hat_l, lmbd_r: float):
+        """_get_optimal_prices under price_start="own": every (type, partition) with EVs runs its loop from
+        its own previous prices, all of a step's loops of both types in ONE
+        compute_optimal_prices_parallel call (price_loops_batched False: the same loops one at a time
+        through compute_optimal_prices, the same bits)."""
+        from .price_solver import compute_optimal_prices_parallel
+
+        if self.group is not None or _settings.PRINT_LEVEL >= 1 or not self._staged:
+            raise ValueError("price_start='own': single process, PRINT_LEVEL 0 and staged partitions "
+                             "(stage_partitions) required")
+        torch = _torch()
+        main = torch.cuda.current_stream(self.device)
+        types = (("Small", self.price_solver_s, self._pstats[0], w_hat_s[:, : self.N_lo]),
+                 ("Large", self.price_solver_l, self._pstats[1], w_hat_l[:, : self.N_lo]))
+        for kind, *_ in types:  # (as the chained path: the layouts' host sync on this thread)
+            self._partition_layout(kind, *self._loop_levels(kind))
+        jobs, where = [], []
+        for kind, solver, st, w_hat in types:
+            for p in range(self.P):
+                if st[p, 0] > 0:
+                    start = self._own_prev.get((kind, p))
+                    jobs.append((solver, p, w_hat[p, :], np.zeros(self.r) if start is None else start))
+                    where.append((kind, p))
+        t0 = time.perf_counter()
+        if self.price_loops_batched:
+            res = compute_optimal_prices_parallel(jobs, lmbd_r)
+        else:
+            res = []
+            for solver, p, w_ref, start in jobs:
+                solver.use_partition(p)
+                solver.prev_prices = np.array(start, dtype=np.float64)
+                lm, stats = solver.compute_optimal_prices(w_ref, lmbd_r)
+                res.append((lm.copy(), stats))
+            for _, solver, *_ in types:
+                main.wait_stream(solver._stream)
+        dt = (time.perf_counter() - t0) * 1e3
+        self.chain_ms = {"Small": dt, "Large": dt}
+        if self.profile_phases:
+            self.phase_ms["prices/own/optimal_prices"] = self.phase_ms.get("prices/own/optimal_prices", 0.0) + dt
+        out = {"Small": (np.zeros((self.P, self.r)), [{} for _ in range(self.P)]),
+               "Large": (np.zeros((self.P, self.r)), [{} for _ in range(self.P)])}
+        for (kind, p), (lm, stats) in zip(where, res):
+            out[kind][0][p, :] = lm[: self.r]
+            out[kind][1][p] = stats
+            self._own_prev[(kind, p)] = np.array(lm[: self.r], dtype=np.float64)
+        return out["Small"][0], out["Large"][0], out["Small"][1], out["Large"][1]
 
     def _stage_partitions(self):
         """Every partition's loop plan of this step, prepared (PriceSolver.stage_partition) on one

@@ -111,6 +111,7 @@ class PriceSolver:
         self._plan_w0m = None  # get_w0_price0_many's scalar-pass plan
         self._w0m_live = False
         self._staged = {}  # partition -> its loop plan and levels (stage_partition / use_partition)
+        self._blocks = {}  # partition -> its own price block (compute_optimal_prices_parallel)
         self._A_bar = None
         self._A_bar_inv = None
         self._kappa = None
@@ -477,6 +478,21 @@ class PriceSolver:
                                 "dual_cost_decrease_predicted": dec[k, 1, :m].copy()}))
         return out
 
+    def _price_block(self, p: int):
+        """Partition p's own price block for compute_optimal_prices_parallel, made the first time that
+        API sees the partition: device [8N + 2] (prices | lmbd_r | w_ref), pinned staging, pinned set
+        outputs.  The solver's shared ``_in`` stays what the single loop uses."""
+        blk = self._blocks.get(p)
+        if blk is None:
+            torch = _torch()
+            n_in = 8 * self.N + 2
+            blk = self._blocks[p] = {
+                "dev_in": torch.zeros(n_in, dtype=torch.float64, device=self._dev),
+                "host_in": torch.zeros(n_in, dtype=torch.float64).pin_memory(),
+                "host_sw": torch.zeros((2, self.N), dtype=torch.float64).pin_memory(),
+                "host_st": torch.zeros((2, _lib.LOMPC_SET_STATS), dtype=torch.float64).pin_memory()}
+        return blk
+
     def _native_loop(self, lmbd_k, lmbd_r, w_ref, A_bar, tol):
         """price_solver.py:106-140 in ONE call (lompc_price_loop): plan runs, copies, syncs and
         price steps stay in C++ until convergence."""
@@ -743,3 +759,101 @@ class PriceSolver:
         for k in range(K):
             self._check_stats(st[k])
         return out["w0"], st[:, 0, _lib.LOMPC_STAT_SUM_PRICE0].copy()
+
+
+def compute_optimal_prices_parallel(jobs, lmbd_r: float, max_parts_per_launch: int = 0):
+    """INDEPENDENT price loops side by side, in ONE native call (lompc_price_loops, regularize = 1): the
+    loops the persistent device form takes share persistent launches (k_loop_runs), every other one runs
+    as a single loop inside the same call.  ``jobs``: [(solver, partition, w_ref (N,), start prices (r,))]
+    over staged partitions (``stage_partition``) of one or more PriceSolvers on one device.  Returns per
+    job (lmbd (3N,), solver_stats), bit for bit what ``solver.compute_optimal_prices(w_ref, lmbd_r)``
+    reports for that partition with ``prev_prices`` set to the job's start prices.  No solver's
+    ``prev_prices`` is read or written: the start prices are the caller's.  Each partition works on a
+    price block of its own (``PriceSolver._price_block``).  The preconditions are ``chain_ok``'s;
+    otherwise ValueError.  ``max_parts_per_launch`` > 0 lowers the loops per launch (A/B timing)."""
+    jobs = list(jobs)
+    n = len(jobs)
+    if n == 0:
+        return []
+    torch = _torch()
+    MAX = _settings.MAX_PRICE_SOLVER_ITERATIONS
+    if _settings.PRINT_LEVEL >= 1:
+        raise ValueError("compute_optimal_prices_parallel: PRINT_LEVEL must be 0 (nothing is printed per loop)")
+    seen = set()
+    for ps, p, _, _ in jobs:
+        if ps.group is not None:
+            raise ValueError("compute_optimal_prices_parallel: a sharded solver (process group)")
+        if not ps.native_loop:
+            raise ValueError("compute_optimal_prices_parallel: native_loop is off")
+        st = ps._staged.get(p)
+        if st is None or st["_plan"] is None:
+            raise ValueError(f"compute_optimal_prices_parallel: partition {p} is not staged (stage_partition)")
+        if st["_plan"].direct:
+            raise ValueError(f"compute_optimal_prices_parallel: partition {p}'s plan is a DIRECT-mode plan")
+        if ps.lompc.device != jobs[0][0].lompc.device:
+            raise ValueError("compute_optimal_prices_parallel: solvers on different devices")
+        if (id(ps), p) in seen:
+            raise ValueError(f"compute_optimal_prices_parallel: partition {p} of one solver twice")
+        seen.add((id(ps), p))
+    arr = (_lib.PriceLoopsPart * n)()
+    keep = []  # (the arrays the native call reads and writes)
+    out_buf = []
+    metric = {}
+    for k, (ps, p, w_ref, start) in enumerate(jobs):
+        N, r = ps.N, ps.r
+        if id(ps) not in metric:
+            A_bar, A_bar_inv = ps._get_w_inner_product_metric(lmbd_r)
+            metric[id(ps)] = (np.ascontiguousarray(A_bar, dtype=np.float64), float(ps._kappa_of(A_bar_inv)))
+        A_bar, kappa = metric[id(ps)]
+        st = ps._staged[p]
+        plan = st["_plan"]
+        plan._usable()
+        blk = ps._price_block(p)
+        tol = np.sqrt(N) * st["y0_rng"] + ps.eps_tol  # get_robustness_bounds (price_solver.py:182-186)
+        w_ref = np.ascontiguousarray(np.asarray(w_ref, dtype=np.float64).reshape(N))
+        start = np.asarray(start, dtype=np.float64).reshape(r)
+        lm, wk, dec = np.zeros(3 * N), np.zeros(N), np.zeros((2, MAX))
+        lm[:r] = start
+        args = _lib.PriceLoopArgs(
+            N, r, MAX, 1 if _settings.PRICE_SOLVER_TOL_TYPE != "max" else 0, float(ps.consts.theta),
+            float(ps.consts.w_max), float(ps.m), kappa, float(ps.eps_reg), float(tol), float(st["nEVs"]),
+            float(lmbd_r), A_bar.ctypes.data, w_ref.ctypes.data, blk["dev_in"].data_ptr(), blk["host_in"].data_ptr(),
+            plan.out["set_sum_w"].data_ptr(), plan.out["set_stats"].data_ptr(), blk["host_sw"].data_ptr(),
+            blk["host_st"].data_ptr(), None, 1 if ps.device_loop else 0)
+        keep.append((args, w_ref, A_bar))
+        out_buf.append((lm, wk, dec))
+        q = arr[k]
+        q.plan = plan._plan.value
+        q.args = ctypes.addressof(args)
+        q.lmbd, q.w_k = lm.ctypes.data, wk.ctypes.data
+        q.dec_actual, q.dec_pred = dec[0].ctypes.data, dec[1].ctypes.data
+        q.regularize = 1
+    dev = jobs[0][0].lompc.device
+    lib = jobs[0][0]._lib
+    cur = torch.cuda.current_stream(dev)
+    for ps in {id(j[0]): j[0] for j in jobs}.values():
+        cur.wait_stream(ps._stream)  # (the partitions were staged on their solvers' streams)
+    launches = ctypes.c_int(0)
+    rc = lib.lompc_price_loops(n, ctypes.cast(arr, ctypes.c_void_p), int(max_parts_per_launch),
+                               ctypes.byref(launches), cur.cuda_stream)
+    for k, (ps, *_rest) in enumerate(jobs):
+        if not arr[k].rc:
+            ps.n_batched_calls += int(arr[k].calls)
+    if rc != _lib.LOMPC_OK:
+        k = next((k for k in range(n) if arr[k].rc), None)
+        text = lib.lompc_plan_last_error(arr[k].plan).decode(errors="replace") if k is not None else ""
+        if rc == _lib.LOMPC_ERR_NOT_CONVERGED:
+            raise SolverError(text)
+        if "gamma" in text:
+            raise AssertionError(text)
+        raise ValueError(text or _lib.status_text(lib, None, rc))
+    out = []
+    for k in range(n):
+        q = arr[k]
+        lm, _, dec = out_buf[k]
+        m = q.calls - 1  # (decreases recorded: one per step taken)
+        out.append((lm, {"iter": int(q.iterations), "price_before_reg": float(q.price_before_reg),
+                         "price_after_reg": float(q.price_after_reg),
+                         "dual_cost_decrease_actual": dec[0, :m].copy(),
+                         "dual_cost_decrease_predicted": dec[1, :m].copy()}))
+    return out

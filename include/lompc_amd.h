@@ -526,6 +526,48 @@ typedef struct lompc_price_chain_part {
 int lompc_price_chain(int n_parts, lompc_price_chain_part* parts, const lompc_price_loop_args* common,
                       double* prev_prices, void* stream);
 
+/* L INDEPENDENT price loops in one call: a sweep over targets, the two EV types, the partitions of a
+ * station started from their own previous prices, Monte-Carlo populations.  Every part's outputs carry
+ * the bits of lompc_price_loop(plan, args, ...) on the same inputs (lmbd, w_k, dual_cost, errs, the
+ * `iterations` decreases; iterations = its *iterations, calls = iterations + 1), whatever the other
+ * parts are and however the call is split into launches.  With regularize = 1 the outputs are those of
+ * lompc_price_chain for a one-part chain started from lmbd[:r] (start prices past r dropped, iterations
+ * the reference's loop variable, lompc_price_regularize on the result, price_before_reg /
+ * price_after_reg); regularize = 0 leaves the two price_* fields alone.
+ * Which parts share a launch: the parts the persistent device loop takes (device_loop = 1, A_bar =
+ * A'A + kappa I, a gamma-sorted one-rank plan of at most 32 cells per set) run CONCURRENTLY, those of
+ * equal N, r and cell count as one persistent launch of n x 2 x cells one-wave workgroups (kernel
+ * k_loop_runs: each wave runs the single loop's body on its own loop's buffers; no object is shared
+ * between loops, a loop that ends leaves while the others go on).  A launch holds at most as many loops
+ * as fit in HALF of the kernel's resident workgroups on the device (occupancy query; other streams'
+ * kernels may hold places), and at most max_parts_per_launch when that is > 0 (tests, A/B timing);
+ * further parts follow as consecutive launches on the stream, in part order.  *launches (may be NULL):
+ * the persistent launches issued.  Every other part (sharded plan, more than 32 cells, another A_bar,
+ * device_loop = 0) runs through lompc_price_loop, one at a time, within the same call.
+ * Reference w: in this call a loop reads its reference w from ITS OWN price buffer (dev_in + 6N + 2,
+ * both sets, staged from args->w_ref), not from the w_ref pointer its plan was created with — concurrent
+ * loops of one solver's partitions have different targets, and re-targeting a plan (lompc_plan_update)
+ * would re-measure its windows.  For a plan created on its price buffer's w_ref view (as PriceSolver
+ * creates them) the two coincide; args->prof is accumulated only by parts that take the single loop.
+ * Errors: every part has its own rc with lompc_price_loop's meanings; the call returns the first
+ * non-zero rc in part order; the other parts' outputs are valid, a failed part writes none, and every
+ * plan is ready for its next loop afterwards, as above.  Refused (LOMPC_ERR_INVALID_ARG) before anything
+ * is launched or written: n_parts < 0, a NULL plan / args / lmbd / w_k or NULL buffer of args that
+ * lompc_price_loop requires, the same plan in two parts, two parts whose dev_in (or host_in) ranges
+ * [8N + 2] overlap, plans on different devices.  n_parts == 0 returns LOMPC_OK.  No device allocation
+ * in the steady state: a second call of the same shape allocates nothing. */
+typedef struct lompc_price_loops_part {
+  lompc_plan* plan;                       /* a loop plan: [this partition's EVs | the central QP] */
+  const lompc_price_loop_args* args;      /* this loop's own arguments, own dev_in / host_in / host_sw / host_st */
+  double* lmbd;                           /* host [3N]  in: start prices, out: final prices */
+  double* w_k; double* dec_actual; double* dec_pred;   /* as lompc_price_loop (dec_* may be NULL) */
+  int regularize;                         /* 1: lompc_price_regularize on the result, as lompc_price_chain does */
+  int iterations, calls, rc, pad;         /* out, as lompc_price_chain_part */
+  double dual_cost, price_before_reg, price_after_reg, errs[3];   /* out */
+} lompc_price_loops_part;
+int lompc_price_loops(int n_parts, lompc_price_loops_part* parts, int max_parts_per_launch,
+                      int* launches, void* stream);
+
 /* The regularisation step alone (price_solver.py:142-147 with :248-255; replaces the CVXPY call of
  * price_regularizer.py:68-85 for the station's A = Dphi(w)', b = A lmbd, c = phi(w)): lmbd host [3N]
  * in / out (lmbd[:r] replaced), w host [N] the loop's final iterate, *pre / *post = phi(w)'lmbd

@@ -1,6 +1,7 @@
 """Diagnostic: where the time of one closed-loop ChargingStation step goes (bench.py's
 BiMPC steps/sec leg, config-5 shape).  Prints per-phase wall times and a cProfile
-summary of the timed steps."""
+summary of the timed steps.  Environment: N (horizon, 48), M2 (EVs per type, 131072; config 5:
+1048576), PRICE_START ("chained", or "own": the station mode whose loops share launches)."""
 import cProfile
 import os
 import pstats
@@ -23,7 +24,7 @@ torch.cuda.set_device(0)
 consts = station_consts(4, M_2, n_lo=N, n_bi=N, demand_scale=DEMAND_SCALE * M_2 / NUM_EVS_PER_EV_TYPE,
                         u_b_max=0.5, x_max=0.5)
 np.random.seed(0)
-st = ChargingStation(consts, device=0)
+st = ChargingStation(consts, device=0, price_start=os.environ.get("PRICE_START", "chained"))  # ("own": the batched loops)
 phases = {}
 for name in ("_get_bimpc_solution", "_get_optimal_prices", "_get_w0_price0", "_update_state", "_update_logs"):
     f = getattr(st, name)

@@ -503,8 +503,8 @@ class BatchPlan:
 
     def info(self) -> dict:
         """Batch size, parameter sets, gamma cells per set, k_eval workgroups of the plan, the runs per
-        stepped run_steps launch (1 once the stepped form has run, else 0) and whether run_steps' wide
-        form evaluates through k_evals_st (the stager wave: set reductions grouped by seven row waves);
+        stepped run_steps launch (1 once the stepped form has run, else 0); evals_staged: always False (the
+        evaluation form it reported has been removed; the key is kept for its readers);
         ring_runs: the runs whose path tables the wide form's table ring may hold at once; tail_launches: the
         fused launches of its run_steps calls so far (k_evals_tail: a group's evaluations with the next
         group's paths behind them; 0 where every group took its own k_paths launch)."""
@@ -517,7 +517,7 @@ class BatchPlan:
         ring, tail = ctypes.c_int64(0), ctypes.c_int64(0)
         self._check_rc(self._lib.lompc_plan_get_wide_info(self._plan, ctypes.byref(ring), ctypes.byref(tail)))
         return {"B": B.value, "sets": S.value, "cells": cells.value, "workgroups": wg.value,
-                "steps_group": min(grp.value, 1), "evals_staged": grp.value == 2, "ring_runs": ring.value,
+                "steps_group": grp.value, "evals_staged": False, "ring_runs": ring.value,
                 "tail_launches": tail.value}
 
     def update(self, gamma, set_offsets, w_ref=None, validate=True) -> "BatchPlan":

@@ -11,6 +11,12 @@ register and spill counts and the static LDS from the code object's metadata.
 
 The compile takes a few minutes (the file instantiates every plan kernel).  --asm reads an assembly file
 written earlier (--keep) instead of compiling.
+
+    python scripts/isa_census.py --diff PARENT.s BRANCH.s [--rename 'REGEX=REPL' ...]
+
+compares two --keep files kernel by kernel, for a change that must leave the generated code as it is: the
+kernels in only one file, those whose normalised text differs (with the first differing lines) and those whose
+kernel descriptor or resource counts differ; the exit status is non-zero if a kernel of both files differs.
 """
 import argparse
 import json
@@ -98,6 +104,60 @@ def census(asm_text, wanted):
     return rows
 
 
+def split_kernels(asm_text, renames):
+    """kernel symbol -> (normalised body lines, descriptor {directive: value}).  Normalised away, because a
+    kernel's place in the file or a renamed template sets them: comments, trailing blanks, the function index of
+    .LBB<n>_ / .Ltmp<n> / .Lfunc_end<n>, the file-wide counter of .Lpost_getpc<n> (renumbered from the kernel's
+    first) and the --rename substitutions."""
+    for pat, repl in renames:
+        asm_text = re.sub(pat, repl, asm_text)
+    out = {}
+    for m in re.finditer(r"\n\t\.amdhsa_kernel (\S+)\n(.*?)\n\t\.end_amdhsa_kernel", asm_text, re.S):
+        sym = m.group(1)
+        desc = dict(line.split()[:2] for line in m.group(2).split("\n"))
+        # (and the resource counts set behind the function: num_vgpr, num_agpr, numbered_sgpr, private_seg_size, ...)
+        desc.update((".amdhsa_" + k, v) for k, v in re.findall(rf"\n\t\.set {re.escape(sym)}\.(\w+), (\S+)", asm_text))
+        text = re.search(rf"\n{re.escape(sym)}:.*?\n\.Lfunc_end\d+:", asm_text, re.S).group(0)
+        text = text.replace(m.group(0), "")  # (the descriptor sits inside the function's text: compared apart)
+        getpc = {}
+        body = []
+        for line in text.split("\n"):
+            line = re.sub(r"\.(LBB|Ltmp|Lfunc_end)\d+", r".\1#", line.split(";")[0].rstrip())
+            line = re.sub(r"\.Lpost_getpc(\d+)", lambda g: ".Lpost_getpc#%d" % getpc.setdefault(g.group(1), len(getpc)), line)
+            if line:
+                body.append(line)
+        out[sym] = (body, desc)
+    return out
+
+
+def diff_asm(parent, branch, renames):
+    """Compare two --keep files kernel by kernel (text only); the exit status: 1 if a kernel of both differs."""
+    with open(parent) as f:
+        pk = split_kernels(f.read(), renames)
+    with open(branch) as f:
+        bk = split_kernels(f.read(), renames)
+    names = demangle(sorted(set(pk) | set(bk)))
+    short = lambda s: norm(names[s])
+    for tag, only in (("parent", sorted(set(pk) - set(bk))), ("branch", sorted(set(bk) - set(pk)))):
+        print(f"only in the {tag}: {len(only)}" + "".join(f"\n  {short(s)}" for s in only))
+    both = sorted(set(pk) & set(bk))
+    n_text = n_desc = 0
+    for s in both:
+        (pb, pd), (bb, bd) = pk[s], bk[s]
+        if pb != bb:
+            n_text += 1
+            i = next((k for k, (x, y) in enumerate(zip(pb, bb)) if x != y), min(len(pb), len(bb)))
+            print(f"text differs: {short(s)}: {len(pb)} -> {len(bb)} lines, first at line {i + 1}")
+            for k in range(i, i + 3):
+                print(f"  - {pb[k] if k < len(pb) else ''}\n  + {bb[k] if k < len(bb) else ''}")
+        dd = [k for k in sorted(set(pd) | set(bd)) if pd.get(k) != bd.get(k)]
+        if dd:
+            n_desc += 1
+            print(f"descriptor differs: {short(s)}: " + ", ".join(f"{k[8:]} {pd.get(k)} -> {bd.get(k)}" for k in dd))
+    print(f"in both: {len(both)} kernels; instruction text differs in {n_text}; descriptor differs in {n_desc}")
+    return 1 if n_text or n_desc else 0
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("-D", dest="defines", action="append", default=[])
@@ -105,7 +165,12 @@ def main():
     ap.add_argument("--asm", help="read this assembly file instead of compiling")
     ap.add_argument("--keep", help="keep the assembly here")
     ap.add_argument("--json", action="store_true")
+    ap.add_argument("--diff", nargs=2, metavar=("PARENT.s", "BRANCH.s"), help="compare two --keep files kernel by kernel")
+    ap.add_argument("--rename", action="append", default=[], metavar="REGEX=REPL",
+                    help="--diff: a symbol rename applied to both files before they are compared")
     a = ap.parse_args()
+    if a.diff:
+        sys.exit(diff_asm(a.diff[0], a.diff[1], [r.split("=", 1) for r in a.rename]))
     if a.asm:
         path = a.asm
     else:

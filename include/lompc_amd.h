@@ -588,7 +588,11 @@ int lompc_price_regularize(int N, int r, double theta, double w_max, const doubl
  * phi/Dphi of lompc.py:172-187 truncated to the first r = 2N or 3N rows.
  *   w_ref, w [N]; lmbd [r]  ->  lmbd_next [r]
  *   *dual_cost_decrease = (lmbd'P lmbd + q'lmbd) - (x'Px + q'x)      (:236, :244-245)
- *   *iterations = active-set iterations used (may be NULL)
+ *   *iterations = active-set iterations used (may be NULL).  The rounds of the primal-dual active
+ *     set (at most 64, from lmbd's free set) are counted first and the rounds of the primal active
+ *     set from x = 0, which runs only when the first method ends without a certified point, on top of
+ *     them: a value above 64 means that the primal fallback ran.  Near the price loop's fixed point
+ *     (w_ref within rounding of w) that is routine; tests/price_step_cases.py relies on the count.
  * Exact (finite active-set method), KKT-certified; LOMPC_ERR_NOT_CONVERGED
  * otherwise (cvxpy SolverError).  The certificate's tolerance is 1e-11 (1 + max |q|); the reduced
  * solves' error grows like theta^2 / (2 eps_reg m) = 1 / (4 eps_reg delta) (1e-8 at delta = 1e-4),

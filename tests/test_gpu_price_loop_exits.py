@@ -55,7 +55,9 @@ chain under K_CHAIN = 8 — small N 24: 4, 7 (stopped; 62 uncapped), 3; large N 
 (closest 3.1e-4).
 
 Left out: err = 3 (a price QP without a certificate) — no input is known that reaches it, and none is
-searched for on the GPU; world sizes above 1 (one GPU: the RCCL path runs at world size 1).
+searched for on the GPU (the price QP's primal fallback, the half of it that runs when the primal-dual active
+set does not end, is steered and checked in test_gpu_price_step_cases.py: it certifies on every case there);
+world sizes above 1 (one GPU: the RCCL path runs at world size 1).
 """
 import contextlib
 import ctypes

@@ -37,21 +37,24 @@ OUT_KEYS = ("it", "calls", "lm", "w_k", "dual", "dec", "errs")
 class Spec:
     """One loop's inputs; build() makes a fresh solver (plan + price block) on them."""
 
-    def __init__(self, N, ev, pt, cells, y0, w_ref, lr=0.0, start=None, max_iter=CAP, device_loop=True, bad=None):
+    def __init__(self, N, ev, pt, cells, y0, w_ref, lr=0.0, start=None, max_iter=CAP, device_loop=True, bad=None,
+                 tol=None, lc=None):
         self.N, self.ev, self.pt, self.cells = N, ev, pt, cells
         self.y0, self.w_ref, self.lr, self.max_iter, self.device_loop, self.bad = y0, w_ref, lr, max_iter, device_loop, bad
+        self.tol = tol  # the loop's tolerance instead of get_robustness_bounds' (loop_args)
+        self.lc = lc    # LoMPCConstants other than the shipped set ``ev`` names
         self.r = (2 if pt == "linear" else 3) * N
         self.start = np.zeros(self.r) if start is None else np.asarray(start, dtype=np.float64)[: self.r].copy()
 
     def but(self, **kw):
         s = Spec(self.N, self.ev, self.pt, self.cells, self.y0, self.w_ref, self.lr, self.start, self.max_iter,
-                 self.device_loop, self.bad)
+                 self.device_loop, self.bad, self.tol, self.lc)
         for k, v in kw.items():
             setattr(s, k, v)
         return s
 
     def build(self):
-        _, lc = consts(self.ev)
+        lc = consts(self.ev)[1] if self.lc is None else self.lc
         ps = solver(self.N, lc, self.pt, self.cells, device_loop=self.device_loop)
         set_levels(ps, self)
         return ps
@@ -74,9 +77,12 @@ def make(N, ev, pt, cells, nev, seed, lo=0.35, width=0.04, robust=False, **kw):
     return Spec(N, ev, pt, cells, y0, w_ref, lr=1.5 * N * c.delta if robust else 0.0, **kw)
 
 
-def loop_args(ps, spec, dev_in=None, host_in=None, dev_sw=None, dev_st=None):
-    """lompc_price_loop_args as PriceSolver._native_loop fills them: (args, what they point to)."""
-    tol, _ = ps.get_robustness_bounds(spec.lr)
+def loop_args(ps, spec, dev_in=None, host_in=None, dev_sw=None, dev_st=None, tol=None):
+    """lompc_price_loop_args as PriceSolver._native_loop fills them: (args, what they point to).  ``tol`` (or
+    the spec's) replaces the tolerance of get_robustness_bounds."""
+    tol = spec.tol if tol is None else tol
+    if tol is None:
+        tol, _ = ps.get_robustness_bounds(spec.lr)
     A_bar, A_bar_inv = ps._get_w_inner_product_metric(spec.lr)
     A_bar = np.ascontiguousarray(A_bar, dtype=np.float64)
     w_ref = np.ascontiguousarray(spec.w_ref, dtype=np.float64)

@@ -1,6 +1,7 @@
 """CPU tests of the host-side price iteration solvers in the C-ABI library
 (no device needed): the price-gradient QP (price_solver.py:216-246) against the
-dense numpy/scipy restatement (oracle/price_oracle.py), its KKT certificate, and
+dense numpy/scipy restatement (oracle/price_oracle.py), its KKT certificate — on random draws and on
+the committed cases of tests/price_step_cases.py, where the QP's primal fallback runs — and
 the regularizer LP (price_regularizer.py:68-85) against HiGHS, plus the reference
 test's own invariants (test_price_regularizer.py:13-14)."""
 import ctypes
@@ -10,6 +11,7 @@ import pytest
 
 import lompc_oracle as O
 import price_oracle as PO
+import price_step_cases as PSC
 from lompc_amd import _lib
 from lompc_amd.price_regularizer import PriceRegularizer, PriceRegularizerError
 
@@ -95,6 +97,49 @@ def test_price_step_small_delta_matches_dense_oracle(case):
     assert np.max(np.abs(x - xo)) <= bar_x
     assert abs(dec - deco) <= 1e-13 * mags
     assert dec >= -1e-13 * mags  # a descent step never increases the majorizer
+
+
+@pytest.mark.parametrize("case", PSC.committed(), ids=lambda c: c.id)
+def test_price_step_cases_match_dense_oracle(case):
+    """The committed cases of tests/price_step_cases.py: near the loop's fixed point the step's primal-dual
+    active set does not end and its primal fallback runs (``iterations > 64``, asserted for every fallback-family
+    case), which no random draw above reaches; the control cases end in the first half at the same shapes.  The
+    bars are test_price_step_small_delta_matches_dense_oracle's, derived there: KKT residual of the dense problem
+    <= 1e-9 (1 + max |q|), distance to the dense oracle <= sqrt(r) (rho_e + rho_o) / (2 eps), the decrease within
+    1e-13 of the magnitudes of its dense sums and not below minus that.  Prints each case's share of its bars."""
+    assert PSC.CONSTS["a2"] == SMALL_DELTA[1]
+    rc, x, dec, it = PSC.host_step(case)
+    assert rc == 0, rc
+    assert (it > PSC.PDAS_ROUNDS) == (case.family != "control"), it
+    P, q, _ = PSC.dense(case)
+    xo, deco = PSC.dense_oracle(case)
+    lmbd = case.start[: case.r]
+    rho_e, rho_o = PO.price_qp_kkt(P, q, x), PO.price_qp_kkt(P, q, xo)
+    bar_kkt = 1e-9 * (1.0 + np.max(np.abs(q)))
+    bar_x = np.sqrt(case.r) * (rho_e + rho_o) / (2 * PO.EPS_REG)
+    mags = abs(lmbd @ P @ lmbd) + abs(q @ lmbd) + abs(x @ P @ x) + abs(q @ x)
+    dx, ddec = np.max(np.abs(x - xo)), abs(dec - deco)
+    print(f"{case.id}: iterations {it}; KKT {rho_e:.2e} = {rho_e / bar_kkt:.3f} of its bar (oracle {rho_o:.2e}); "
+          f"|dx| {dx:.2e} = {dx / bar_x if bar_x else 0.0:.3f} of its bar; |ddec| {ddec:.2e} = {ddec / (1e-13 * mags):.4f} of its bar")
+    assert np.all(x >= 0) and rho_e <= bar_kkt
+    assert dx <= bar_x
+    assert ddec <= 1e-13 * mags
+    assert dec >= -1e-13 * mags
+
+
+def test_price_step_cases_cover_the_grid():
+    """The coverage condition of the committed table: every cell has its control, and each of the 29 cells where
+    the fallback is routine (all A2-like cells, the shipped-large lmbd_r = 0 cells other than N 64, r 2N) has at
+    least one fallback case."""
+    cells = PSC.cells()
+    assert list(PSC.SEEDS) == cells and len(cells) == 60
+    assert sum(PSC.required(c) for c in cells) == 29
+    for cell in cells:
+        seeds = PSC.SEEDS[cell]
+        assert len(seeds) == len(PSC.FAMILIES) and seeds[-1] is not None, cell
+        assert all(s is None or s in PSC.SEED_RANGE for s in seeds), cell
+        if PSC.required(cell):
+            assert any(s is not None for s in seeds[:-1]), cell
 
 
 def test_price_step_fixed_point():

@@ -382,6 +382,18 @@ void plan_prof_end(lompc_plan* p, int k, hipEvent_t e0, hipEvent_t e1, int launc
   p->prof_ev[k].push_back(e1);
   p->prof_mult[k].push_back(launches);
 }
+// One launch with its profile events: the event pair of kernel k (null when k is not profiled, or when
+// `carry` is false — a launch that carries no events at all, LOMPC_STEPS_SPAN_EVENTS past the first
+// group), launch(e0, e1) (a hipExtLaunchKernelGGL), the launch check, and the pair recorded as `launches`.
+template <typename Launch>
+int timed_launch(lompc_plan* p, int k, int launches, bool carry, Launch&& launch) {
+  hipEvent_t e0 = nullptr, e1 = nullptr;
+  if (carry && plan_prof_begin(p, k, &e0, &e1)) return fail_arg(p, "profiling events");
+  launch(e0, e1);
+  HIPCHK(p, hipGetLastError());
+  if (carry) plan_prof_end(p, k, e0, e1, launches);
+  return LOMPC_OK;
+}
 
 #ifdef LQ_PREP_PROF  // diagnostic builds: lq_plan_prepare's phases on stderr (host microseconds)
 #define LQ_PREP_MARK(k) prep_t[k] = std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now().time_since_epoch()).count()
@@ -675,16 +687,21 @@ int lq_launch_path(lompc_plan* p, const double* lmbd, const double* lmbd_r, cons
                    const FinalArgs* fin = nullptr) {
   if (!lmbd || !lmbd_r) return fail_arg(p, "run: lmbd and lmbd_r required");
   const PathArgs pa = path_args(p, lmbd, lmbd_r, tb);
-  hipEvent_t e0 = nullptr, e1 = nullptr;
-  if (plan_prof_begin(p, LOMPC_PLAN_K_PATH, &e0, &e1)) return fail_arg(p, "profiling events");
   const unsigned ncell = (unsigned)(p->S * p->G);
-  if (fin)
-    hipExtLaunchKernelGGL(path_fin_kernel(p->N), dim3(ncell + (unsigned)p->S), dim3(64), 0, st, e0, e1, 0, pa, *fin);
-  else
-    hipExtLaunchKernelGGL(path_kernel(p->N), dim3(ncell), dim3(64), 0, st, e0, e1, 0, pa);
-  HIPCHK(p, hipGetLastError());
-  plan_prof_end(p, LOMPC_PLAN_K_PATH, e0, e1);
-  return LOMPC_OK;
+  return timed_launch(p, LOMPC_PLAN_K_PATH, 1, true, [&](hipEvent_t e0, hipEvent_t e1) {
+    if (fin)
+      hipExtLaunchKernelGGL(path_fin_kernel(p->N), dim3(ncell + (unsigned)p->S), dim3(64), 0, st, e0, e1, 0, pa, *fin);
+    else
+      hipExtLaunchKernelGGL(path_kernel(p->N), dim3(ncell), dim3(64), 0, st, e0, e1, 0, pa);
+  });
+}
+
+// k_agg's / k_aggs' / the price loops' arguments from path table `tb` into the given set outputs
+AggArgs agg_args(const lompc_plan* p, const double* lmbd, const double* lmbd_r, const PathTab& tb, double* set_sum_w,
+                 double* set_stats, const int* skip) {
+  return AggArgs{(int)p->S, p->G, p->N, p->aggF, p->d_q, p->ce, p->d_set_off, p->d_window, p->gamma, lmbd, lmbd_r,
+                 p->w_ref, tb.cnt, tb.lo, tb.sl, tb.ge, tb.cf, tb.ab, p->d_P, p->B + p->S, p->d_pos,
+                 p->d_sinfo, set_sum_w, set_stats, p->d_stats, p->d_tally, skip};
 }
 
 // the rest of one run from the path table `tb`: k_eval (or k_agg) and k_finalize, then with a
@@ -818,24 +835,19 @@ int lq_launch_eval(lompc_plan* p, const double* lmbd, const double* lmbd_r, doub
                       !set_sum_w && (cost || w0 || status || set_stats) && !xr && !agg && !defer && !prof_ctx &&
                       p->nblk > 0 && p->scalar_cells >= 1;
   const bool close = !agg && !scalar && (p->close || (p->close_no_w && !w)) && p->nblk > 0;
+  int rc = LOMPC_OK;
   if (agg) {  // timed as k_eval
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    if (plan_prof_begin(p, LOMPC_PLAN_K_EVAL, &e0, &e1)) return fail_arg(p, "profiling events");
-    AggArgs ga{(int)p->S, p->G, N, p->aggF, p->d_q, p->ce, p->d_set_off, p->d_window, p->gamma, lmbd, lmbd_r,
-               p->w_ref, tb.cnt, tb.lo, tb.sl, tb.ge, tb.cf, tb.ab, p->d_P, p->B + p->S, p->d_pos,
-               p->d_sinfo, r.set_sum_w, r.set_stats, p->d_stats, p->d_tally, p->skip};
+    const AggArgs ga = agg_args(p, lmbd, lmbd_r, tb, r.set_sum_w, r.set_stats, p->skip);
     const int nw = std::min(p->G, (int)LQ_AGG_W);
-    hipExtLaunchKernelGGL(agg_kernel(N), dim3((unsigned)p->S), dim3(64 * nw), 0, st, e0, e1, 0, ga);
-    HIPCHK(p, hipGetLastError());
-    plan_prof_end(p, LOMPC_PLAN_K_EVAL, e0, e1);
+    rc = timed_launch(p, LOMPC_PLAN_K_EVAL, 1, true, [&](hipEvent_t e0, hipEvent_t e1) {
+      hipExtLaunchKernelGGL(agg_kernel(N), dim3((unsigned)p->S), dim3(64 * nw), 0, st, e0, e1, 0, ga);
+    });
   } else if (scalar) {
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    if (plan_prof_begin(p, LOMPC_PLAN_K_SCALAR, &e0, &e1)) return fail_arg(p, "profiling events");
-    hipExtLaunchKernelGGL(k_scalar, dim3((unsigned)p->nblk), dim3(EVAL_EVS), scalar_lds(p->G, p->scalar_cells), st, e0, e1,
-                          0, a, p->scalar_cells);
-    HIPCHK(p, hipGetLastError());
-    plan_prof_end(p, LOMPC_PLAN_K_SCALAR, e0, e1);
-  } else if (p->nblk > 0) {
+    rc = timed_launch(p, LOMPC_PLAN_K_SCALAR, 1, true, [&](hipEvent_t e0, hipEvent_t e1) {
+      hipExtLaunchKernelGGL(k_scalar, dim3((unsigned)p->nblk), dim3(EVAL_EVS), scalar_lds(p->G, p->scalar_cells), st, e0,
+                            e1, 0, a, p->scalar_cells);
+    });
+  } else if (p->nblk > 0) {  // (hand-written: lompc_solve_batch's runs are timed on their context, not the plan)
     hipEvent_t e0 = nullptr, e1 = nullptr;
     if (cprof ? take_events(prof_ctx->prof_pool, &e0, &e1) : plan_prof_begin(p, LOMPC_PLAN_K_EVAL, &e0, &e1))
       return fail_arg(p, "profiling events");
@@ -853,17 +865,16 @@ int lq_launch_eval(lompc_plan* p, const double* lmbd, const double* lmbd_r, doub
       plan_prof_end(p, LOMPC_PLAN_K_EVAL, e0, e1);
     }
   }
+  if (rc) return rc;
   if (!close && !agg && defer && !xr && N + NPX <= 64) {  // (one-wave closing: a record fits the wave)
     *defer = r;
     return LOMPC_OK;
   }
-  if (!close && !agg) {  // (else the sets were closed inside k_eval / k_agg)
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    if (plan_prof_begin(p, LOMPC_PLAN_K_FINAL, &e0, &e1)) return fail_arg(p, "profiling events");
-    hipExtLaunchKernelGGL(k_finalize, dim3((unsigned)p->S), dim3(256), 0, st, e0, e1, 0, r);
-    HIPCHK(p, hipGetLastError());
-    plan_prof_end(p, LOMPC_PLAN_K_FINAL, e0, e1);
-  }
+  if (!close && !agg &&  // (else the sets were closed inside k_eval / k_agg)
+      (rc = timed_launch(p, LOMPC_PLAN_K_FINAL, 1, true, [&](hipEvent_t e0, hipEvent_t e1) {
+         hipExtLaunchKernelGGL(k_finalize, dim3((unsigned)p->S), dim3(256), 0, st, e0, e1, 0, r);
+       })))
+    return rc;
   if (!xr) return LOMPC_OK;
   return lq_exchange(p, p->d_xsend, set_sum_w, set_stats, st);
 }
@@ -903,20 +914,15 @@ int lq_launch_loop(lompc_plan* p, const double* lmbd, const double* lmbd_r, doub
   if (rr) return rr;
   const PathTab tb = own_tab(p);
   const PathArgs pa = path_args(p, lmbd, lmbd_r, tb);
-  AggArgs ga{(int)p->S, p->G, N, p->aggF, p->d_q, p->ce, p->d_set_off, p->d_window, p->gamma, lmbd, lmbd_r,
-             p->w_ref, tb.cnt, tb.lo, tb.sl, tb.ge, tb.cf, tb.ab, p->d_P, p->B + p->S, p->d_pos,
-             p->d_sinfo, set_sum_w, set_stats, p->d_stats, p->d_tally, p->skip};
-  hipEvent_t e0 = nullptr, e1 = nullptr;  // (timed as k_path)
-  if (plan_prof_begin(p, LOMPC_PLAN_K_PATH, &e0, &e1)) return fail_arg(p, "profiling events");
-  if (persistent)  // (S * G one-wave workgroups: all resident at once, whatever else runs)
-    hipExtLaunchKernelGGL(loop_run_kernel(N), dim3((unsigned)(p->S * p->G)), dim3(64), 0, st, e0, e1, 0, pa, ga, sa,
-                          p->d_aggrec);
-  else
-    hipExtLaunchKernelGGL(loop_iter_kernel(N), dim3((unsigned)(p->S * p->G)), dim3(64), 0, st, e0, e1, 0, pa, ga, sa,
-                          p->d_aggrec, m);
-  HIPCHK(p, hipGetLastError());
-  plan_prof_end(p, LOMPC_PLAN_K_PATH, e0, e1);
-  return LOMPC_OK;
+  const AggArgs ga = agg_args(p, lmbd, lmbd_r, tb, set_sum_w, set_stats, p->skip);
+  return timed_launch(p, LOMPC_PLAN_K_PATH, 1, true, [&](hipEvent_t e0, hipEvent_t e1) {  // (timed as k_path)
+    if (persistent)  // (S * G one-wave workgroups: all resident at once, whatever else runs)
+      hipExtLaunchKernelGGL(loop_run_kernel(N), dim3((unsigned)(p->S * p->G)), dim3(64), 0, st, e0, e1, 0, pa, ga, sa,
+                            p->d_aggrec);
+    else
+      hipExtLaunchKernelGGL(loop_iter_kernel(N), dim3((unsigned)(p->S * p->G)), dim3(64), 0, st, e0, e1, 0, pa, ga, sa,
+                            p->d_aggrec, m);
+  });
 }
 
 // the plan's cell records, grown to its cell count, their zero record zeroed (on the stream)
@@ -954,12 +960,9 @@ int lq_loop_job_fill(lompc_plan* p, const double* dev_in, double* set_sum_w, dou
   const int N = p->N;
   const double *lmbd = dev_in, *lmbd_r = dev_in + 6 * N, *w_ref = dev_in + 6 * N + 2;
   const PathTab tb = own_tab(p);
-  LoopJob job{path_args(p, lmbd, lmbd_r, tb),
-              AggArgs{(int)p->S, p->G, N, p->aggF, p->d_q, p->ce, p->d_set_off, p->d_window, p->gamma, lmbd, lmbd_r,
-                      w_ref, tb.cnt, tb.lo, tb.sl, tb.ge, tb.cf, tb.ab, p->d_P, p->B + p->S, p->d_pos,
-                      p->d_sinfo, set_sum_w, set_stats, p->d_stats, p->d_tally, p->skip},
-              sa, p->d_aggrec};
-  job.pa.w_ref = w_ref;
+  LoopJob job{path_args(p, lmbd, lmbd_r, tb), agg_args(p, lmbd, lmbd_r, tb, set_sum_w, set_stats, p->skip), sa,
+              p->d_aggrec};
+  job.pa.w_ref = job.ga.w_ref = w_ref;
   memcpy(slot, &job, sizeof(job));
   return LOMPC_OK;
 }
@@ -1354,211 +1357,249 @@ int wide_ring(lompc_plan* p, hipStream_t st) {
   return LOMPC_OK;
 }
 
-// K >= 1 independent runs.  Two schedules, one per plan kind:
-// * wide (no warm start — every run's path depends on its own prices only): the paths of up to
-//   LQ_WIDE_RUNS runs in ONE k_paths launch, then launch k (0 <= k <= K) = k_step(run k's evaluation
-//   (k < K), run k - 1's closing (k >= 1)), the next runs' paths launched before the first launch that
-//   needs them.  Run j's tables sit in ring slot j % (LQ_WIDE_RUNS + 1) (a slot is rewritten only after
-//   its run has closed), records j % 2.  K + 1 evaluation / closing launches + ceil(K / LQ_WIDE_RUNS)
-//   path launches.
-// * stepped (warm-started plans: run j + 1's path starts from run j's working sets): launch 0 = run
-//   0's path; launch k (1 <= k <= K) = k_step(run k's path (k < K), run k - 1's evaluation, run k - 2's
-//   closing (k >= 2)); launch K + 1 = run K - 1's closing.  Run j uses path table j % 2, records j % 2
-//   and cell-start working sets j % 3.
-// Per-EV outputs: run k writes w + k ev_stride N (cost, w0, status + k ev_stride); with ev_stride = 0
-// every run writes the same rows and only the LAST run's closing writes per-EV outputs (every earlier
-// closing shares its launch with a later run's evaluation, whose rows must win).  Set outputs of run
-// k at the per-run strides.  With a communicator, run j's closing fills send slot j % 2 and its
-// all-gather + combine follow the launch that carried it, on the same stream (one collective per run).
-// split (LOMPC_STEPS_PER_KERNEL): every launch above issued as one launch per part (path / evaluation
-// / closing), in that order — the same kernels on the same arguments without the overlap, so the same
-// bits (what the bench's verification compares).  span: one event pair from the start of the first
-// steady launch's dispatch (the first that carries an evaluation and a closing) to the end of the last
-// steady one of the first path group (hipExtLaunchKernel events), read as that many launches.
-int lq_run_steps_stepped(lompc_plan* p, const double* lmbd, int64_t lmbd_stride, const double* lmbd_r,
-                         int64_t lmbd_r_stride, int n_runs, int profile_every, bool span_events, double* w, double* cost,
-                         double* w0, int8_t* status, int64_t ev_stride, double* set_sum_w, int64_t sw_stride,
-                         double* set_stats, int64_t st_stride, bool split, hipStream_t st, bool scalar = false) {
+// ---------------------------------------------------------------- lompc_plan_run_steps: K independent runs
+// Outputs, in every schedule below: run j reads the prices lm(j), lr(j) and writes its set outputs at the
+// per-run strides; its per-EV outputs at w + j ev_stride N (cost, w0, status + j ev_stride).  With
+// ev_stride = 0 every run writes the same rows and only the LAST run's closing writes per-EV outputs (an
+// earlier closing may share its launch with a later run's evaluation, whose rows must win).
+namespace {
+
+// One lompc_plan_run_steps call as every schedule takes it: the caller's arguments, the steps flags
+// decoded (span: LOMPC_STEPS_SPAN_EVENTS, split: LOMPC_STEPS_PER_KERNEL) and the entry point's decisions
+// (wide: the plan takes the wide forms; scalar: the call takes the wide scalar form).
+struct StepsCall {
+  const double* lmbd;
+  int64_t lmbd_stride;
+  const double* lmbd_r;
+  int64_t lmbd_r_stride;
+  int K, profile_every;
+  bool span, split, wide, scalar;
+  double *w, *cost, *w0;
+  int8_t* status;
+  int64_t ev_stride;
+  double* set_sum_w;
+  int64_t sw_stride;
+  double* set_stats;
+  int64_t st_stride;
+  hipStream_t st;
+  const double* lm(int j) const { return lmbd + (size_t)j * lmbd_stride; }
+  const double* lr(int j) const { return lmbd_r + (size_t)j * lmbd_r_stride; }
+  double* sw_of(int j) const { return set_sum_w ? set_sum_w + (size_t)j * sw_stride : nullptr; }
+  double* st_of(int j) const { return set_stats ? set_stats + (size_t)j * st_stride : nullptr; }
+  // run j's part of the per-EV output x of `width` values per EV (a null output stays null)
+  template <typename T>
+  T* ev_of(T* x, int j, int width = 1) const {
+    return x ? x + (size_t)j * ev_stride * width : nullptr;
+  }
+};
+
+// the wide forms' runs per path launch for a call of K runs (< 1: the plan is too big for two ring slots)
+int wide_group(const lompc_plan* p, int K) { return (int)std::min<int64_t>({(int64_t)K, LQ_WIDE_RUNS, wide_fit(p)}); }
+
+// What the k_evals and k_step schedules need before their first launch, in this order: the stepped state
+// (block map, tables, records) of the plan's kind, a communicator's two send slots, the wide table ring.
+int steps_setup(lompc_plan* p, bool wide, hipStream_t st) {
   auto& z = p->stp;
   int rc;
-  const int N = p->N;
-  const int64_t ncell = p->S * p->G, L = p->S * (N + LOMPC_SET_STATS);
-  const int K = n_runs;
-  // wide: runs per path launch (wide_fit); a plan too big for two table slots takes the stepped form
-  const int64_t fit = wide_fit(p);
-  const int Kc = (int)std::min<int64_t>({(int64_t)K, LQ_WIDE_RUNS, fit});
-  const bool wide = (p->flags & LOMPC_PLAN_WARM_START) == 0 && Kc >= 1;
-  const int slots = Kc + 1;
   if ((!z.ok || z.wide != wide) && (rc = stepped_setup(p, st, wide))) return rc;
+  if (p->comm && (rc = lq_xbufs(p, 2))) return rc;
+  return wide ? wide_ring(p, st) : LOMPC_OK;
+}
+
+// the stepped state's block map and one slot of its records in place of the plan's own (eval_args')
+void bind_stepped(const lompc_plan::Stepped& z, double* part, int* fcnt, int* fidx, EvalArgs& a, FinalArgs& r) {
+  a.blk = reinterpret_cast<const int4*>(z.d_map);
+  a.nblk = z.nblk;
+  a.partial = part;
+  r.partial = part;
+  a.fail_cnt = fcnt;
+  r.fail_cnt = fcnt;
+  a.fail_idx = fidx;
+  r.fail_idx = fidx;
+  r.blk_prefix = reinterpret_cast<const int*>(z.d_map + (((size_t)z.nblk * sizeof(int4) + 15) & ~(size_t)15));
+}
+
+// k_paths: the paths of runs g0 .. g0 + n - 1 into the table ring, run j in slot j % slots; one K_PATH
+// pair read as `launches`
+int launch_paths(lompc_plan* p, const StepsCall& c, int g0, int n, int slots, int launches = 1) {
+  const PathArgs pw = path_args(p, c.lmbd, c.lmbd_r, p->stp.wt);
+  const int64_t ncell = p->S * p->G;
+  return timed_launch(p, LOMPC_PLAN_K_PATH, launches, true, [&](hipEvent_t e0, hipEvent_t e1) {
+    hipExtLaunchKernelGGL(paths_kernel(p->N), dim3((unsigned)(n * ncell)), dim3(64), 0, c.st, e0, e1, 0, pw, c.lmbd_stride,
+                          c.lmbd_r_stride, g0, slots);
+  });
+}
+
+// With a communicator, behind the closings of runs g0 .. g0 + n - 1 into their contiguous send records: ONE
+// all-gather of the n records and one rank-ordered combine into the caller's set outputs.
+int exchange_runs(lompc_plan* p, const StepsCall& c, int g0, int n) {
+  const int64_t tot = (int64_t)n * p->S * (p->N + LOMPC_SET_STATS);
+  if (const int rc = lq_comm_allgather(p->comm, p->d_xsend, p->d_xrecv, (size_t)tot, c.st)) {
+    p->err = p->comm->err;
+    return rc;
+  }
+  if (c.set_sum_w || c.set_stats) {
+    const CombineRunsArgs ca{p->d_xrecv, p->comm->nranks, n, (int)p->S, p->N, g0, c.K - 1, c.set_sum_w, c.set_stats,
+                             c.sw_stride, c.st_stride};
+    hipLaunchKernelGGL(k_combine_runs, dim3((unsigned)std::max<int64_t>(1, std::min<int64_t>((tot + 255) / 256, 1024))),
+                       dim3(256), 0, c.st, ca);
+    HIPCHK(p, hipGetLastError());
+  }
+  return LOMPC_OK;
+}
+
+// The batched wide form (plans without warm starts: every run's path depends on its own prices only).  Per
+// group of n <= grp runs THREE launches: k_paths (the n paths into the table ring, run j in slot j % slots),
+// k_evals (the n evaluations, each workgroup through its block of every run, into the group's record slots
+// j - g0) and k_closes (the n x S closings); with a communicator the group's closings fill contiguous send
+// records and ONE all-gather and combine follow.  The runs are independent, so the group size changes no bits.
+// * tail (LQ_WIDE_TAIL_PATHS): with a second group and a ring that holds two, only group 0 takes a k_paths
+//   launch; group g + 1's paths ride behind group g's evaluations in ONE k_evals_tail launch, counted as a
+//   K_PATH launch with its time inside the K_EVAL pair, and in z.tail_launches.
+// * scalar (LOMPC_STEPS_SCALAR_PASS, the rule of lompc_amd.h): k_scalars instead of k_evals, one workgroup
+//   per (run, block) on the same block map and record slots, timed as K_SCALAR; every launch of the form
+//   is read as its runs, and no launch is fused.
+// * split (LOMPC_STEPS_PER_KERNEL; the entry point sends it here only without w, and for the scalar form):
+//   one run per group, so one part per launch.  Runs without w sum the certified pieces instead of rows, so
+//   only these kernels give them the wide form's bits.
+// Events: k_paths one K_PATH pair; the evaluation one K_EVAL (K_SCALAR) pair read as n launches — with span
+// only the first group's —; k_closes one K_FINAL pair read as n.
+int lq_steps_wide(lompc_plan* p, const StepsCall& c) {
+  auto& z = p->stp;
+  int rc;
+  const int N = p->N, K = c.K, Kc = wide_group(p, K);
+  const int64_t ncell = p->S * p->G, L = p->S * (N + LOMPC_SET_STATS);
   const bool xr = p->comm != nullptr;
-  if (xr && (rc = lq_xbufs(p, 2))) return rc;
-  if (wide && (rc = wide_ring(p, st))) return rc;
+  if ((rc = steps_setup(p, true, c.st))) return rc;
+  // record slots x blocks, bounded like the table ring: a run's slot holds every block's record, its
+  // re-solve counts and its re-solve list (EVAL_MAXB indices per block), so a batch of many blocks
+  // takes smaller groups instead of gigabytes of mostly empty lists
+  const int64_t rec_run = (int64_t)z.nblk * ((N + NPX) * 8 + EVAL_WAVES * 4 + EVAL_MAXB * 4);
+  const int64_t kr =
+      std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(LQ_WIDE_RUNS, wide_fit(p)), LQ_WIDE_BYTES / rec_run));
+  const int64_t need = kr * z.nblk;
+  if (need > z.cap_rrec) {
+    if ((rc = grow(p, &z.rpart, need * (N + NPX))) || (rc = grow(p, &z.rfcnt, need * EVAL_WAVES)) ||
+        (rc = grow(p, &z.rfidx, need * EVAL_MAXB)))
+      return rc;
+    // (touched once here, as the table ring)
+    HIPCHK(p, hipMemsetAsync(z.rpart, 0, (size_t)need * (N + NPX) * sizeof(*z.rpart), c.st));
+    HIPCHK(p, hipMemsetAsync(z.rfcnt, 0, (size_t)need * EVAL_WAVES * sizeof(*z.rfcnt), c.st));
+    HIPCHK(p, hipMemsetAsync(z.rfidx, 0, (size_t)need * EVAL_MAXB * sizeof(*z.rfidx), c.st));
+    z.cap_rrec = need;
+  }
+  if (xr && (rc = lq_xbufs(p, Kc, Kc))) return rc;
+  // run 0's arguments on ring slot 0 and record slot 0: the kernels offset them per run
+  EvalArgs ea;
+  FinalArgs ff;
+  eval_args(p, c.lmbd, c.lmbd_r, c.w, c.cost, c.w0, c.status, z.wt, ea, ff);
+  ea.piece_sums = c.w ? 0 : 1;  // (no rows to store: the per-stage sums from the piece aggregates)
+  bind_stepped(z, z.rpart, z.rfcnt, z.rfidx, ea, ff);
+  ff.set_sum_w = xr ? p->d_xsend : c.set_sum_w;
+  ff.set_stats = xr ? p->d_xsend + p->S * N : c.set_stats;
+  const int grp = c.split ? 1 : (int)std::min<int64_t>(Kc, kr);
+  // (the ring is sized for the plan's largest group, which a smaller group's two may still exceed)
+  const bool tail = LQ_WIDE_TAIL_PATHS && !c.split && !c.scalar && K > grp && p->G % LQ_STEP_CELLS == 0 &&
+                    wide_slots(p, grp) == 2 * (int64_t)grp && 2 * (int64_t)grp * ncell <= z.cap_wt;
+  const int slots = tail ? 2 * grp : Kc + 1;
+  const size_t lds = eval_lds(N, p->G, p->cap);
+  const int kk = c.scalar ? LOMPC_PLAN_K_SCALAR : LOMPC_PLAN_K_EVAL;
+  for (int g0 = 0; g0 < K; g0 += grp) {
+    const int n = std::min(grp, K - g0);
+    const int np = tail ? std::max(0, std::min(grp, K - g0 - grp)) : 0;  // the next group's runs, behind this one's
+    if ((!tail || g0 == 0) && (rc = launch_paths(p, c, g0, n, slots, c.scalar ? n : 1))) return rc;
+    const EvalsArgs x{g0, n, slots, z.nblk, c.lmbd_stride, c.lmbd_r_stride, c.ev_stride, ncell};
+    rc = timed_launch(p, kk, n, !c.span || g0 == 0, [&](hipEvent_t e0, hipEvent_t e1) {
+      if (c.scalar) {
+        hipExtLaunchKernelGGL(k_scalars, dim3((unsigned)(n * z.nblk)), dim3(EVAL_EVS), scalar_lds(p->G, p->scalar_cells),
+                              c.st, e0, e1, 0, ea, x, p->scalar_cells, K - 1);
+      } else if (np > 0) {
+        const PathArgs pw = path_args(p, c.lmbd, c.lmbd_r, z.wt);
+        const int64_t npw = (int64_t)((np + LQ_TAIL_RUNS - 1) / LQ_TAIL_RUNS) * (ncell / LQ_STEP_CELLS);
+        hipExtLaunchKernelGGL(evals_tail_kernel(N), dim3((unsigned)(z.nblk + npw)), dim3(EVAL_EVS), lds, c.st, e0, e1, 0,
+                              ea, x, pw, g0 + grp, np);
+        if ((p->prof >> LOMPC_PLAN_K_PATH) & 1) p->prof_n[LOMPC_PLAN_K_PATH] += 1;
+        z.tail_launches += 1;
+      } else {
+        hipExtLaunchKernelGGL(evals_kernel(N), dim3((unsigned)z.nblk), dim3(EVAL_EVS), lds, c.st, e0, e1, 0, ea, x);
+      }
+    });
+    if (rc) return rc;
+    const ClosesArgs cl{g0, n, slots, z.nblk, (int)p->S, K - 1, xr ? 1 : 0, c.lmbd_stride, c.lmbd_r_stride, c.ev_stride,
+                        xr ? L : c.sw_stride, xr ? L : c.st_stride, ncell};
+    rc = timed_launch(p, LOMPC_PLAN_K_FINAL, n, true, [&](hipEvent_t e0, hipEvent_t e1) {
+      hipExtLaunchKernelGGL(k_closes, dim3((unsigned)(n * p->S)), dim3(256), 0, c.st, e0, e1, 0, ff, cl);
+    });
+    if (rc || (xr && (rc = exchange_runs(p, c, g0, n)))) return rc;
+  }
+  return LOMPC_OK;
+}
+
+// The k_step loop: one launch per run that carries parts of consecutive runs.  Two plan kinds share it:
+// * stepped (warm-started plans: run j + 1's path starts from run j's working sets): launch 0 = run 0's
+//   path; launch k (1 <= k <= K) = k_step(run k's path (k < K), run k - 1's evaluation, run k - 2's closing
+//   (k >= 2)); launch K + 1 = run K - 1's closing.  Run j uses path table j % 2, records j % 2 and
+//   cell-start working sets j % 3 (a closing re-solves from run j's while run j + 2's path writes).
+// * wide with split and w (LOMPC_STEPS_PER_KERNEL's reference for the batched form with rows): the paths of
+//   up to Kc runs in ONE k_paths launch before the first launch that needs them, run j in ring slot
+//   j % (Kc + 1); launch k (0 <= k <= K) = k_step(run k's evaluation (k < K), run k - 1's closing (k >= 1)),
+//   records j % 2.
+// split: every launch issued as one launch per part (path / evaluation / closing), in that order — the same
+// kernel on the same arguments without the overlap, so the same bits.  With a communicator, run j's closing
+// fills send slot j % 2 and its all-gather + combine follow the launch that carried it (one per run).
+// Events (K_EVAL): the steady launches 1 .. K - 1 (split: their evaluation part), every profile_every-th of
+// them when sampled; span: ONE pair from the first steady launch to the last steady one of the first path
+// group (stepped: of the call), read as that many launches.  k_paths launches carry a K_PATH pair each.
+int lq_steps_kstep(lompc_plan* p, const StepsCall& c) {
+  auto& z = p->stp;
+  int rc;
+  const int N = p->N, K = c.K, Kc = wide_group(p, K);
+  const bool wide = c.wide, xr = p->comm != nullptr;
+  const int64_t ncell = p->S * p->G, L = p->S * (N + LOMPC_SET_STATS);
+  const int slots = Kc + 1;  // (wide) a path group and the run before it
+  if ((rc = steps_setup(p, wide, c.st))) return rc;
   auto tab = [&](int j) {
+    PathTab t;
     if (wide) {  // ring slot j % slots
       const int64_t o = (int64_t)(j % slots) * ncell;
-      PathTab t;
       t.cnt = z.wt.cnt + o;
       t.lo = z.wt.lo + o;
       t.ge = z.wt.ge + o * LQ_PPL;
       t.cf = z.wt.cf + o * LQ_PPL * 8;
       t.ab = z.wt.ab + o * LQ_PPL * N;
       t.sl = z.wt.sl + o * 64;
-      return t;
+    } else {
+      t = z.tab[j & 1];
+      t.sl = z.sl3 + (size_t)(j % 3) * ncell * 64;
     }
-    PathTab t = z.tab[j & 1];
-    t.sl = z.sl3 + (size_t)(j % 3) * ncell * 64;
     return t;
   };
-  auto lm = [&](int j) { return lmbd + (size_t)j * lmbd_stride; };
-  auto lr = [&](int j) { return lmbd_r + (size_t)j * lmbd_r_stride; };
-  auto sw_of = [&](int j) { return set_sum_w ? set_sum_w + (size_t)j * sw_stride : nullptr; };
-  auto st_of = [&](int j) { return set_stats ? set_stats + (size_t)j * st_stride : nullptr; };
   auto xsend = [&](int j) { return p->d_xsend + (size_t)(j & 1) * L; };
   auto args = [&](int j, EvalArgs& a, FinalArgs& r) {
-    const size_t eo = (size_t)j * ev_stride;
-    eval_args(p, lm(j), lr(j), w ? w + eo * N : nullptr, cost ? cost + eo : nullptr, w0 ? w0 + eo : nullptr,
-              status ? status + eo : nullptr, tab(j), a, r);
-    a.blk = reinterpret_cast<const int4*>(z.d_map);
-    a.nblk = z.nblk;
-    a.partial = z.part[j & 1];
-    r.partial = z.part[j & 1];
-    a.fail_cnt = z.fcnt[j & 1];
-    r.fail_cnt = z.fcnt[j & 1];
-    a.fail_idx = z.fidx[j & 1];
-    r.fail_idx = z.fidx[j & 1];
-    r.blk_prefix = reinterpret_cast<const int*>(z.d_map + (((size_t)z.nblk * sizeof(int4) + 15) & ~(size_t)15));
-    r.set_sum_w = xr ? xsend(j) : sw_of(j);
-    r.set_stats = xr ? xsend(j) + p->S * N : st_of(j);
-    if (ev_stride == 0 && j != K - 1) {  // (its re-solved rows would race a later evaluation's)
+    eval_args(p, c.lm(j), c.lr(j), c.ev_of(c.w, j, N), c.ev_of(c.cost, j), c.ev_of(c.w0, j), c.ev_of(c.status, j), tab(j),
+              a, r);
+    bind_stepped(z, z.part[j & 1], z.fcnt[j & 1], z.fidx[j & 1], a, r);
+    r.set_sum_w = xr ? xsend(j) : c.sw_of(j);
+    r.set_stats = xr ? xsend(j) + p->S * N : c.st_of(j);
+    if (c.ev_stride == 0 && j != K - 1) {  // (its re-solved rows would race a later evaluation's)
       r.w = r.cost = r.w0 = nullptr;
       r.status = nullptr;
     }
   };
   const size_t lds = eval_lds(N, p->G, p->cap);
   const StepKernel kern = step_kernel(N);
-  // (split runs without w output take the batched launches one run per group too: their evaluation
-  // sums the certified pieces instead of rows, so only these kernels give the wide form's bits)
-  if (wide && (!split || !w)) {
-    // batched: per path group of n <= Kc runs THREE launches — k_paths (the n paths), k_evals (the n
-    // evaluations, each workgroup through its block of every run) and k_closes (the n x S closings);
-    // the same kernels' arithmetic as the split form below, so the same bits
-    // (tail, below: from the second group on the paths ride in the launch before, k_evals_tail)
-    // (scalar — LOMPC_STEPS_SCALAR_PASS, the rule of lompc_amd.h: k_scalars instead of k_evals, one workgroup
-    // per (run, block) on the same block map and record slots, timed as K_SCALAR)
-    // record slots x blocks, bounded like the table ring: a run's slot holds every block's record, its
-    // re-solve counts and its re-solve list (EVAL_MAXB indices per block), so a batch of many blocks
-    // takes smaller groups instead of gigabytes of mostly empty lists (the runs are independent: the
-    // group size changes no bits)
-    const int64_t rec_run = (int64_t)z.nblk * ((N + NPX) * 8 + EVAL_WAVES * 4 + EVAL_MAXB * 4);
-    const int64_t kr = std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(LQ_WIDE_RUNS, fit), LQ_WIDE_BYTES / rec_run));
-    const int64_t need = kr * z.nblk;
-    if (need > z.cap_rrec) {
-      if ((rc = grow(p, &z.rpart, need * (N + NPX))) || (rc = grow(p, &z.rfcnt, need * EVAL_WAVES)) ||
-          (rc = grow(p, &z.rfidx, need * EVAL_MAXB)))
-        return rc;
-      // (touched once here, as the table ring)
-      HIPCHK(p, hipMemsetAsync(z.rpart, 0, (size_t)need * (N + NPX) * sizeof(*z.rpart), st));
-      HIPCHK(p, hipMemsetAsync(z.rfcnt, 0, (size_t)need * EVAL_WAVES * sizeof(*z.rfcnt), st));
-      HIPCHK(p, hipMemsetAsync(z.rfidx, 0, (size_t)need * EVAL_MAXB * sizeof(*z.rfidx), st));
-      z.cap_rrec = need;
-    }
-    if (xr && (rc = lq_xbufs(p, Kc, Kc))) return rc;
-    EvalArgs ea;
-    FinalArgs ff;
-    eval_args(p, lmbd, lmbd_r, w, cost, w0, status, tab(0), ea, ff);
-    ea.piece_sums = w ? 0 : 1;  // (no rows to store: the per-stage sums from the piece aggregates)
-    ea.blk = reinterpret_cast<const int4*>(z.d_map);
-    ea.nblk = z.nblk;
-    ea.partial = z.rpart;
-    ff.partial = z.rpart;
-    ea.fail_cnt = z.rfcnt;
-    ff.fail_cnt = z.rfcnt;
-    ea.fail_idx = z.rfidx;
-    ff.fail_idx = z.rfidx;
-    ff.blk_prefix = reinterpret_cast<const int*>(z.d_map + (((size_t)z.nblk * sizeof(int4) + 15) & ~(size_t)15));
-    ff.set_sum_w = xr ? p->d_xsend : set_sum_w;
-    ff.set_stats = xr ? p->d_xsend + p->S * N : set_stats;
-    const int grp = split ? 1 : (int)std::min<int64_t>(Kc, kr);
-    // tail (LQ_WIDE_TAIL_PATHS): with a second group, and a ring that holds two groups (wide_slots; the ring is
-    // sized for the plan's largest group, which a smaller group's two may still exceed), group g + 1's paths
-    // ride behind group g's evaluations in one k_evals_tail launch: k_paths(group 0), then per group
-    // k_evals_tail (the last group: k_evals) and k_closes.  Else a k_paths launch before every k_evals.
-    const bool tail = LQ_WIDE_TAIL_PATHS && !split && !scalar && K > grp && p->G % LQ_STEP_CELLS == 0 &&
-                      wide_slots(p, grp) == 2 * (int64_t)grp && 2 * (int64_t)grp * ncell <= z.cap_wt;
-    const int slots = tail ? 2 * grp : Kc + 1;
-    for (int g0 = 0; g0 < K; g0 += grp) {
-      const int n = std::min(grp, K - g0);
-      const int np = tail ? std::max(0, std::min(grp, K - g0 - grp)) : 0;  // the next group's runs, behind this one's
-      if (!tail || g0 == 0) {
-        PathArgs pw = path_args(p, lmbd, lmbd_r, z.wt);
-        hipEvent_t e0 = nullptr, e1 = nullptr;
-        if (plan_prof_begin(p, LOMPC_PLAN_K_PATH, &e0, &e1)) return fail_arg(p, "profiling events");
-        hipExtLaunchKernelGGL(paths_kernel(N), dim3((unsigned)(n * ncell)), dim3(64), 0, st, e0, e1, 0, pw, lmbd_stride,
-                              lmbd_r_stride, g0, slots);
-        HIPCHK(p, hipGetLastError());
-        plan_prof_end(p, LOMPC_PLAN_K_PATH, e0, e1, scalar ? n : 1);  // (scalar: every launch of the form read as its runs)
-      }
-      {  // the evaluation launch carries the K_EVAL (scalar: K_SCALAR) timing (span: the first group's only), as n runs
-        hipEvent_t e0 = nullptr, e1 = nullptr;
-        const bool ev = !span_events || g0 == 0;
-        const int kk = scalar ? LOMPC_PLAN_K_SCALAR : LOMPC_PLAN_K_EVAL;
-        if (ev && plan_prof_begin(p, kk, &e0, &e1)) return fail_arg(p, "profiling events");
-        const EvalsArgs x{g0, n, slots, z.nblk, lmbd_stride, lmbd_r_stride, ev_stride, ncell};
-        if (scalar) {
-          hipExtLaunchKernelGGL(k_scalars, dim3((unsigned)(n * z.nblk)), dim3(EVAL_EVS), scalar_lds(p->G, p->scalar_cells), st,
-                                e0, e1, 0, ea, x, p->scalar_cells, K - 1);
-        } else if (np > 0) {
-          // (the next group's paths are counted as a K_PATH launch, their time is inside this launch's events)
-          const PathArgs pw = path_args(p, lmbd, lmbd_r, z.wt);
-          const int64_t npw = (int64_t)((np + LQ_TAIL_RUNS - 1) / LQ_TAIL_RUNS) * (ncell / LQ_STEP_CELLS);
-          hipExtLaunchKernelGGL(evals_tail_kernel(N), dim3((unsigned)(z.nblk + npw)), dim3(EVAL_EVS), lds, st, e0, e1, 0, ea,
-                                x, pw, g0 + grp, np);
-          if ((p->prof >> LOMPC_PLAN_K_PATH) & 1) p->prof_n[LOMPC_PLAN_K_PATH] += 1;
-          z.tail_launches += 1;
-        } else
-          hipExtLaunchKernelGGL(evals_kernel(N), dim3((unsigned)z.nblk), dim3(EVAL_EVS), lds, st, e0, e1, 0, ea, x);
-        HIPCHK(p, hipGetLastError());
-        if (ev) plan_prof_end(p, kk, e0, e1, n);
-      }
-      {
-        hipEvent_t e0 = nullptr, e1 = nullptr;
-        if (plan_prof_begin(p, LOMPC_PLAN_K_FINAL, &e0, &e1)) return fail_arg(p, "profiling events");
-        const ClosesArgs c{g0, n, slots, z.nblk, (int)p->S, K - 1, xr ? 1 : 0, lmbd_stride, lmbd_r_stride, ev_stride,
-                           xr ? L : sw_stride, xr ? L : st_stride, ncell};
-        hipExtLaunchKernelGGL(k_closes, dim3((unsigned)(n * p->S)), dim3(256), 0, st, e0, e1, 0, ff, c);
-        HIPCHK(p, hipGetLastError());
-        plan_prof_end(p, LOMPC_PLAN_K_FINAL, e0, e1, n);
-      }
-      if (xr) {  // ONE collective for the group's n runs (their send records are contiguous), one combine
-        if ((rc = lq_comm_allgather(p->comm, p->d_xsend, p->d_xrecv, (size_t)n * L, st))) {
-          p->err = p->comm->err;
-          return rc;
-        }
-        if (set_sum_w || set_stats) {
-          const CombineRunsArgs ca{p->d_xrecv, p->comm->nranks, n, (int)p->S, N, g0, K - 1, set_sum_w, set_stats,
-                                   sw_stride, st_stride};
-          const int64_t tot = (int64_t)n * L;
-          hipLaunchKernelGGL(k_combine_runs, dim3((unsigned)std::max<int64_t>(1, std::min<int64_t>((tot + 255) / 256, 1024))),
-                             dim3(256), 0, st, ca);
-          HIPCHK(p, hipGetLastError());
-        }
-      }
-    }
-    return LOMPC_OK;
-  }
-  // the steady launches 1 .. K - 1 (stepped: path + evaluation + closing; wide: evaluation +
-  // closing); the span events cover 1 .. s_last, wide: the first path group's (no path launch inside)
-  const int s_first = 1, s_last = wide ? Kc - 1 : K - 1;
+  const int s_first = 1, s_last = wide ? Kc - 1 : K - 1;  // the steady launches the span events cover
   hipEvent_t span0 = nullptr, span1 = nullptr;
-  if (span_events && s_last >= s_first && plan_prof_begin(p, LOMPC_PLAN_K_EVAL, &span0, &span1))
+  if (c.span && s_last >= s_first && plan_prof_begin(p, LOMPC_PLAN_K_EVAL, &span0, &span1))
     return fail_arg(p, "profiling events");
-  // one k_step launch of (npw path, ne evaluation, nf closing workgroups); prof: its own event pair
+  // one k_step launch of (npw path, ne evaluation, nf closing workgroups); prof: its own event pair (else it
+  // starts or ends the span, or carries no event)
   auto launch = [&](const PathArgs& pa, const EvalArgs& ea, const FinalArgs& ff, int npw, int ne, int nf, bool prof,
                     hipEvent_t s0, hipEvent_t s1) -> int {
     if (npw + ne + nf == 0) return LOMPC_OK;
     hipEvent_t e0 = s0, e1 = s1;
     if (prof && plan_prof_begin(p, LOMPC_PLAN_K_EVAL, &e0, &e1)) return fail_arg(p, "profiling events");
-    hipExtLaunchKernelGGL(kern, dim3((unsigned)(npw + ne + nf)), dim3(EVAL_EVS), lds, st, e0, e1, 0, pa, ea, ff, npw, ne,
+    hipExtLaunchKernelGGL(kern, dim3((unsigned)(npw + ne + nf)), dim3(EVAL_EVS), lds, c.st, e0, e1, 0, pa, ea, ff, npw, ne,
                           nf);
     HIPCHK(p, hipGetLastError());
     if (prof) plan_prof_end(p, LOMPC_PLAN_K_EVAL, e0, e1);
@@ -1568,43 +1609,26 @@ int lq_run_steps_stepped(lompc_plan* p, const double* lmbd, int64_t lmbd_stride,
   const int last = wide ? K : K + 1;
   for (int k = 0; k <= last; ++k) {
     PathArgs pa{};
-    int npw = 0;
     EvalArgs ea{}, unused_e;
     FinalArgs ff{}, unused_f;
-    int ne = 0, nf = 0;
-    if (wide) {
-      if (k < K && k >= paths_to) {  // the next group's paths, one launch
-        const int n = std::min(Kc, K - k);
-        PathArgs pw = path_args(p, lmbd, lmbd_r, z.wt);
-        hipEvent_t e0 = nullptr, e1 = nullptr;
-        if (plan_prof_begin(p, LOMPC_PLAN_K_PATH, &e0, &e1)) return fail_arg(p, "profiling events");
-        hipExtLaunchKernelGGL(paths_kernel(N), dim3((unsigned)(n * ncell)), dim3(64), 0, st, e0, e1, 0, pw, lmbd_stride,
-                              lmbd_r_stride, k, slots);
-        HIPCHK(p, hipGetLastError());
-        plan_prof_end(p, LOMPC_PLAN_K_PATH, e0, e1);
-        paths_to = k + n;
-      }
-      if (k < K) {
-        args(k, ea, unused_f);
-        ne = z.nblk;
-      }
-      if (k >= 1) {
-        args(k - 1, unused_e, ff);
-        nf = (int)p->S;
-      }
-    } else {
-      if (k < K) {
-        pa = path_args(p, lm(k), lr(k), tab(k));
-        npw = z.np_wg;
-      }
-      if (k >= 1 && k - 1 < K) {
-        args(k - 1, ea, unused_f);
-        ne = z.nblk;
-      }
-      if (k >= 2) {
-        args(k - 2, unused_e, ff);
-        nf = (int)p->S;
-      }
+    int npw = 0, ne = 0, nf = 0;
+    const int ev_run = wide ? k : k - 1, fin_run = ev_run - 1;  // the runs this launch evaluates and closes
+    if (wide && k < K && k >= paths_to) {  // the next group's paths, one launch
+      const int n = std::min(Kc, K - k);
+      if ((rc = launch_paths(p, c, k, n, slots))) return rc;
+      paths_to = k + n;
+    }
+    if (!wide && k < K) {
+      pa = path_args(p, c.lm(k), c.lr(k), tab(k));
+      npw = z.np_wg;
+    }
+    if (ev_run >= 0 && ev_run < K) {
+      args(ev_run, ea, unused_f);
+      ne = z.nblk;
+    }
+    if (fin_run >= 0) {
+      args(fin_run, unused_e, ff);
+      nf = (int)p->S;
     }
     int npw_l = npw;
 #ifdef LQ_STEP_DIAG
@@ -1617,9 +1641,9 @@ int lq_run_steps_stepped(lompc_plan* p, const double* lmbd, int64_t lmbd_stride,
 #endif
     // the steady launches carry the events: sampled, or one pair around all of them
     const bool steady = k >= 1 && k <= K - 1;
-    const bool prof = !span_events && steady && (profile_every <= 0 || (k - 1) % profile_every == 0);
+    const bool prof = !c.span && steady && (c.profile_every <= 0 || (k - 1) % c.profile_every == 0);
     const hipEvent_t s0 = (span0 && k == s_first) ? span0 : nullptr, s1 = (span0 && k == s_last) ? span1 : nullptr;
-    if (split) {  // the same parts, one launch each (no overlap)
+    if (c.split) {  // the same parts, one launch each (no overlap)
       if ((rc = launch(pa, ea, ff, npw_l, 0, 0, false, nullptr, nullptr)) ||
           (rc = launch(pa, ea, ff, 0, ne, 0, prof, s0, s1)) || (rc = launch(pa, ea, ff, 0, 0, nf, false, nullptr, nullptr)))
         return rc;
@@ -1627,72 +1651,67 @@ int lq_run_steps_stepped(lompc_plan* p, const double* lmbd, int64_t lmbd_stride,
       return rc;
     }
     if (s1) plan_prof_end(p, LOMPC_PLAN_K_EVAL, span0, span1, s_last - s_first + 1);
-    const int closed = wide ? k - 1 : k - 2;  // the run closed by this launch
-    if (xr && nf && (rc = lq_exchange(p, xsend(closed), sw_of(closed), st_of(closed), st))) return rc;
+    if (xr && nf && (rc = lq_exchange(p, xsend(fin_run), c.sw_of(fin_run), c.st_of(fin_run), c.st))) return rc;
   }
   return LOMPC_OK;
 }
 
 // Reductions-only runs over gamma-sorted sets (k_agg plans), wide: per group of up to Kc runs TWO
-// launches — k_paths (the group's paths into the table ring, as the wide form) and k_aggs (one
+// launches — k_paths (the group's paths into the table ring, run j in slot j % (Kc + 1)) and k_aggs (one
 // workgroup per (run, set): k_agg's per-piece aggregation on run j's tables).  The same kernels'
-// arithmetic as one k_path + k_agg per run (the sequential form, LOMPC_STEPS_PER_KERNEL), so the same
-// bits.  With a communicator the group's closings fill its contiguous send records: ONE all-gather and
-// one combine per group, as the wide form.  K_EVAL events: the k_aggs launch, as n runs.
-int lq_run_steps_aggs(lompc_plan* p, const double* lmbd, int64_t lmbd_stride, const double* lmbd_r,
-                      int64_t lmbd_r_stride, int K, bool span_events, double* set_sum_w, int64_t sw_stride,
-                      double* set_stats, int64_t st_stride, hipStream_t st) {
+// arithmetic as one k_path + k_agg per run (lq_steps_single, LOMPC_STEPS_PER_KERNEL), so the same bits.
+// With a communicator the group's closings fill its contiguous send records: ONE all-gather and one
+// combine per group.  Events: k_paths one K_PATH pair; the k_aggs launch one K_EVAL pair read as n
+// launches, with span only the first group's.
+int lq_steps_aggs(lompc_plan* p, const StepsCall& c) {
   int rc;
-  const int N = p->N;
-  const int64_t ncell = p->S * p->G, L = p->S * (N + LOMPC_SET_STATS);
-  const int Kc = (int)std::min<int64_t>({(int64_t)K, LQ_WIDE_RUNS, wide_fit(p)});
+  const int N = p->N, K = c.K, Kc = wide_group(p, K);
+  const int64_t L = p->S * (N + LOMPC_SET_STATS);
   const int slots = Kc + 1;
-  if ((rc = wide_ring(p, st))) return rc;
+  if ((rc = wide_ring(p, c.st))) return rc;
   const bool xr = p->comm != nullptr;
   if (xr && (rc = lq_xbufs(p, Kc, Kc))) return rc;
-  const PathTab& wt = p->stp.wt;
-  const PathArgs pw = path_args(p, lmbd, lmbd_r, wt);
-  const AggArgs ga{(int)p->S, p->G, N, p->aggF, p->d_q, p->ce, p->d_set_off, p->d_window, p->gamma, lmbd, lmbd_r,
-                   p->w_ref, wt.cnt, wt.lo, wt.sl, wt.ge, wt.cf, wt.ab, p->d_P, p->B + p->S, p->d_pos,
-                   p->d_sinfo, xr ? p->d_xsend : set_sum_w, xr ? p->d_xsend + p->S * N : set_stats, p->d_stats,
-                   p->d_tally, nullptr};
+  const AggArgs ga = agg_args(p, c.lmbd, c.lmbd_r, p->stp.wt, xr ? p->d_xsend : c.set_sum_w,
+                              xr ? p->d_xsend + p->S * N : c.set_stats, nullptr);
   const int nw = std::min(p->G, (int)LQ_AGG_W);
   for (int g0 = 0; g0 < K; g0 += Kc) {
     const int n = std::min(Kc, K - g0);
-    {
-      hipEvent_t e0 = nullptr, e1 = nullptr;
-      if (plan_prof_begin(p, LOMPC_PLAN_K_PATH, &e0, &e1)) return fail_arg(p, "profiling events");
-      hipExtLaunchKernelGGL(paths_kernel(N), dim3((unsigned)(n * ncell)), dim3(64), 0, st, e0, e1, 0, pw, lmbd_stride,
-                            lmbd_r_stride, g0, slots);
-      HIPCHK(p, hipGetLastError());
-      plan_prof_end(p, LOMPC_PLAN_K_PATH, e0, e1);
-    }
-    {
-      hipEvent_t e0 = nullptr, e1 = nullptr;
-      const bool ev = !span_events || g0 == 0;
-      if (ev && plan_prof_begin(p, LOMPC_PLAN_K_EVAL, &e0, &e1)) return fail_arg(p, "profiling events");
-      const AggsArgs x{g0, slots, K - 1, xr ? 1 : 0, lmbd_stride, lmbd_r_stride, xr ? L : sw_stride, xr ? L : st_stride};
-      hipExtLaunchKernelGGL(aggs_kernel(N), dim3((unsigned)(n * p->S)), dim3(64 * nw), 0, st, e0, e1, 0, ga, x);
-      HIPCHK(p, hipGetLastError());
-      if (ev) plan_prof_end(p, LOMPC_PLAN_K_EVAL, e0, e1, n);
-    }
-    if (xr) {
-      if ((rc = lq_comm_allgather(p->comm, p->d_xsend, p->d_xrecv, (size_t)n * L, st))) {
-        p->err = p->comm->err;
-        return rc;
-      }
-      if (set_sum_w || set_stats) {
-        const CombineRunsArgs ca{p->d_xrecv, p->comm->nranks, n, (int)p->S, N, g0, K - 1, set_sum_w, set_stats,
-                                 sw_stride, st_stride};
-        const int64_t tot = (int64_t)n * L;
-        hipLaunchKernelGGL(k_combine_runs, dim3((unsigned)std::max<int64_t>(1, std::min<int64_t>((tot + 255) / 256, 1024))),
-                           dim3(256), 0, st, ca);
-        HIPCHK(p, hipGetLastError());
-      }
-    }
+    if ((rc = launch_paths(p, c, g0, n, slots))) return rc;
+    const AggsArgs x{g0, slots, K - 1, xr ? 1 : 0, c.lmbd_stride, c.lmbd_r_stride, xr ? L : c.sw_stride, xr ? L : c.st_stride};
+    rc = timed_launch(p, LOMPC_PLAN_K_EVAL, n, !c.span || g0 == 0, [&](hipEvent_t e0, hipEvent_t e1) {
+      hipExtLaunchKernelGGL(aggs_kernel(N), dim3((unsigned)(n * p->S)), dim3(64 * nw), 0, c.st, e0, e1, 0, ga, x);
+    });
+    if (rc || (xr && (rc = exchange_runs(p, c, g0, n)))) return rc;
   }
   return LOMPC_OK;
 }
+
+// One k_path_fin + k_eval (k_agg) per run, for the plans no other schedule takes: run k's closing
+// (k_finalize) rides in run k + 1's path launch (k_path_fin) where a record fits one wave — else, and with a
+// communicator or the sets closed inside k_eval, it follows its run —, and the last run's closes on its
+// own, untimed.  The cell-start working sets alternate halves between runs.  Events: every run's k_path
+// and k_eval carry their own pairs; sampled (profile_every), only every profile_every-th run's do.
+int lq_steps_single(lompc_plan* p, const StepsCall& c) {
+  const int mask = p->prof;  // (restored on every exit)
+  int rc = LOMPC_OK;
+  FinalArgs fin{};
+  fin.N = 0;
+  for (int k = 0; k < c.K && rc == LOMPC_OK; ++k) {
+    if (c.profile_every > 0) p->prof = (k % c.profile_every == 0) ? mask : 0;  // sampled runs carry the events
+    const PathTab tb = own_tab(p, k & 1);
+    if ((rc = lq_launch_path(p, c.lm(k), c.lr(k), tb, c.st, fin.N ? &fin : nullptr))) break;
+    rc = lq_launch_eval(p, c.lm(k), c.lr(k), c.ev_of(c.w, k, p->N), c.ev_of(c.cost, k), c.ev_of(c.w0, k),
+                        c.ev_of(c.status, k), c.sw_of(k), c.st_of(k), tb, c.st, nullptr, &fin);
+  }
+  p->prof = mask;
+  if (rc == LOMPC_OK && fin.N) {  // the last run's closing
+    hipLaunchKernelGGL(k_finalize, dim3((unsigned)p->S), dim3(256), 0, c.st, fin);
+    HIPCHK(p, hipGetLastError());
+  }
+  return rc;
+}
+
+}  // namespace
 
 extern "C" {
 
@@ -1716,58 +1735,34 @@ int lompc_plan_run_steps(lompc_plan* p, const double* lmbd, int64_t lmbd_stride,
   if ((steps_flags & LOMPC_STEPS_SCALAR_PASS) && !(p->flags & LOMPC_PLAN_SCALAR_PASS))
     return fail_arg(p, "run_steps: LOMPC_STEPS_SCALAR_PASS requires a plan created with LOMPC_PLAN_SCALAR_PASS");
   HIPCHK(p, hipSetDevice(p->device));
-  hipStream_t st = (hipStream_t)stream;
-  // stepped form: the k_eval / k_finalize plans (not k_agg, not closed inside k_eval on request),
-  // cells in whole workgroups of one set; runs without w output take it too (their evaluation then
-  // sums the rows it does not store)
+  StepsCall c{lmbd, lmbd_stride, lmbd_r, lmbd_r_stride, n_runs, profile_every,
+              (steps_flags & LOMPC_STEPS_SPAN_EVENTS) != 0, (steps_flags & LOMPC_STEPS_PER_KERNEL) != 0, false, false,
+              w, cost, w0, status, ev_stride, set_sum_w, set_sum_w_stride, set_stats, set_stats_stride,
+              (hipStream_t)stream};
+  // The schedule of the call, first match first.  Every batched schedule needs runs, a batch with EVs and no
+  // device price loop around the plan (its kernels poll the loop's flag); the wide ones a plan without warm
+  // starts (every run's path depends on its own prices only) whose table ring holds two runs or more.
+  const bool some = n_runs >= 1 && !p->skip && p->nblk > 0;
+  c.wide = (p->flags & LOMPC_PLAN_WARM_START) == 0 && wide_fit(p) >= 1;
   const bool per_ev = w || cost || w0 || status;
-  const bool agg = p->sorted && !per_ev;
-  // the wide scalar form (LOMPC_STEPS_SCALAR_PASS on a LOMPC_PLAN_SCALAR_PASS plan, the rule of lompc_amd.h): the
-  // wide form's three launches per group with k_scalars as the evaluation.  A per-call condition that fails
-  // leaves the call exactly as without the flag.
-  const bool scalar = (steps_flags & LOMPC_STEPS_SCALAR_PASS) && !(p->flags & (LOMPC_PLAN_DIAG_REPAIR | LOMPC_PLAN_WARM_START)) &&
-                      wide_fit(p) >= 1 && !w && !set_sum_w && (per_ev || set_stats) && !p->comm && !agg && !p->skip &&
-                      n_runs >= 1 && p->nblk > 0 && p->scalar_cells >= 1;
-  if (scalar)
-    return lq_run_steps_stepped(p, lmbd, lmbd_stride, lmbd_r, lmbd_r_stride, n_runs, profile_every,
-                                (steps_flags & LOMPC_STEPS_SPAN_EVENTS) != 0, nullptr, cost, w0, status, ev_stride, nullptr,
-                                set_sum_w_stride, set_stats, set_stats_stride,
-                                (steps_flags & LOMPC_STEPS_PER_KERNEL) != 0, st, true);
-  // gamma-sorted sets without per-EV output: per group of runs one k_paths and one k_aggs launch
-  // (the sequential form below on request: LOMPC_STEPS_PER_KERNEL, the same bits)
-  if (n_runs >= 1 && !p->skip && agg && p->nblk > 0 && (p->flags & LOMPC_PLAN_WARM_START) == 0 &&
-      !(steps_flags & LOMPC_STEPS_PER_KERNEL) && wide_fit(p) >= 1)
-    return lq_run_steps_aggs(p, lmbd, lmbd_stride, lmbd_r, lmbd_r_stride, n_runs,
-                             (steps_flags & LOMPC_STEPS_SPAN_EVENTS) != 0, set_sum_w, set_sum_w_stride, set_stats,
-                             set_stats_stride, st);
-  if (n_runs >= 1 && !p->skip && !agg && !p->close && p->nblk > 0 && p->G % LQ_STEP_CELLS == 0)
-    return lq_run_steps_stepped(p, lmbd, lmbd_stride, lmbd_r, lmbd_r_stride, n_runs, profile_every,
-                                (steps_flags & LOMPC_STEPS_SPAN_EVENTS) != 0, w, cost, w0, status, ev_stride,
-                                set_sum_w, set_sum_w_stride, set_stats, set_stats_stride,
-                                (steps_flags & LOMPC_STEPS_PER_KERNEL) != 0, st);
-  const int mask = p->prof;
-  int rc = LOMPC_OK;
-  // run k's closing (k_finalize) rides in run k + 1's path launch (k_path_fin); the last run's
-  // closes on its own.  The cell-start working sets alternate halves between runs.
-  FinalArgs fin{};
-  fin.N = 0;
-  for (int k = 0; k < n_runs && rc == LOMPC_OK; ++k) {
-    if (profile_every > 0) p->prof = (k % profile_every == 0) ? mask : 0;  // sampled runs carry the events
-    const double* lm = lmbd + (size_t)k * lmbd_stride;
-    const double* lr = lmbd_r + (size_t)k * lmbd_r_stride;
-    const PathTab tb = own_tab(p, k & 1);
-    if ((rc = lq_launch_path(p, lm, lr, tb, st, fin.N ? &fin : nullptr))) break;
-    const size_t eo = (size_t)k * ev_stride;
-    rc = lq_launch_eval(p, lm, lr, w ? w + eo * p->N : nullptr, cost ? cost + eo : nullptr, w0 ? w0 + eo : nullptr,
-                        status ? status + eo : nullptr, set_sum_w ? set_sum_w + (size_t)k * set_sum_w_stride : nullptr,
-                        set_stats ? set_stats + (size_t)k * set_stats_stride : nullptr, tb, st, nullptr, &fin);
-  }
-  p->prof = mask;
-  if (rc == LOMPC_OK && fin.N) {  // the last run's closing
-    hipLaunchKernelGGL(k_finalize, dim3((unsigned)p->S), dim3(256), 0, st, fin);
-    HIPCHK(p, hipGetLastError());
-  }
-  return rc;
+  const bool agg = p->sorted && !per_ev;  // gamma-sorted sets and no per-EV output: the per-piece aggregation
+  // 1. The wide scalar form (LOMPC_STEPS_SCALAR_PASS on a LOMPC_PLAN_SCALAR_PASS plan, the rule of lompc_amd.h):
+  //    no w row and no per-stage sum asked for, some other output, no communicator.  A per-call condition that
+  //    fails leaves the call exactly as without the flag.
+  c.scalar = (steps_flags & LOMPC_STEPS_SCALAR_PASS) && some && c.wide && !(p->flags & LOMPC_PLAN_DIAG_REPAIR) && !w &&
+             !set_sum_w && (per_ev || set_stats) && !p->comm && !agg && p->scalar_cells >= 1;
+  if (c.scalar) return lq_steps_wide(p, c);
+  // 2. Gamma-sorted sets without per-EV output: k_paths + k_aggs per group of runs (per kernel: rule 4, the
+  //    same bits).
+  if (some && c.wide && agg && !c.split) return lq_steps_aggs(p, c);
+  // 3. The k_eval / k_finalize plans (not k_agg, not closed inside k_eval on request) whose cells fill whole
+  //    k_step workgroups; runs without w output too (their evaluation then sums what it does not store).
+  //    Wide plans take the batched launches — per kernel only without w, where no other kernel gives the
+  //    batched form's bits —, warm-started plans and the per-kernel runs with w the k_step loop.
+  if (some && !agg && !p->close && p->G % LQ_STEP_CELLS == 0)
+    return c.wide && (!c.split || !w) ? lq_steps_wide(p, c) : lq_steps_kstep(p, c);
+  // 4. Everything else, n_runs = 0 included: one k_path_fin + k_eval per run.
+  return lq_steps_single(p, c);
 }
 
 int lompc_plan_run_chain(lompc_plan* p, const double* lmbd0, const double* lmbd_r, const double* w_target, double step,

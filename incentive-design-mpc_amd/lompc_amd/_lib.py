@@ -44,6 +44,7 @@ LOMPC_PLAN_CELLS_SHIFT = 20
 LOMPC_STEPS_PER_KERNEL = 1
 LOMPC_STEPS_SPAN_EVENTS = 2
 LOMPC_STEPS_SCALAR_PASS = 4
+LOMPC_MANY_WARM = 1
 
 
 def LOMPC_PLAN_CELLS(g: int) -> int:
@@ -80,6 +81,7 @@ SIGNATURES = [
     ("lompc_solve_batch", _I, [_P, _L, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     ("lompc_run", _I, [_P, _L, _P, _P, _P, _P, _L, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     ("lompc_solve_host", _I, [_P, _P, _D, _D, _P, _P]),
+    ("lompc_solve_many", _I, [_P, _L, _P, _L, _P, _P, _P, _P, _I, _P, _P, _P, _P, _P, _P, _P, _P]),
     ("lompc_last_status", _I, [_P, _P, _P, _P, _P]),
     ("lompc_profile_enable", _I, [_P, _I]),
     ("lompc_profile_read", _I, [_P, _P, _P, _I]),

@@ -10,7 +10,8 @@ optimal cost including its constant, exactly what ``self.w.value`` /
 ``self.cost.value`` give at lompc.py:154-156.
 
 Added for the batched hot path: ``set_params`` (S parameter sets at once) and
-``solve_batch`` (B QPs in one device call with fused per-set reductions).
+``solve_batch`` (B QPs in one device call with fused per-set reductions), and
+``solve_many`` (K QPs that each have their own prices, in one launch).
 
 All numerics run in the HIP extension (``liblompc_amd.so``); this module only
 moves buffers and maps status codes to the reference's exception types:
@@ -306,6 +307,93 @@ class LoMPC:
                 "LoMPC QPs without a certified optimum"
             raise SolverError(f"{fail.value} EVs failed: {why}")
         return rep.value, fail.value, inv.value
+
+    def solve_many(self, lmbd, lmbd_r, gamma, *, w_ref=None, ws=None, warm: bool = False, want_w: bool = True,
+                   want_cost: bool = True, want_w0: bool = False, want_price0: bool = False,
+                   want_status: bool = False, out: dict | None = None, check: bool = True) -> dict:
+        """K unrelated QPs, each with its own prices, in one launch (lompc_solve_many): what a loop of
+        ``solve_lompc(lmbd[k], lmbd_r[k], gamma[k])`` returns, without the loop.
+
+        lmbd: (K, 3N), or (3N,) shared by every QP; lmbd_r: (K,) or a scalar; gamma: (K,); array-likes or
+        device tensors.  w_ref: (K, N) — the result then carries "err", each QP's A_bar error against its
+        row.  ws: uint8 device tensor (K, 64), written with every QP's final working set; warm=True also
+        starts every solve from it (prices iterated per EV).
+        Returns a dict of device tensors: "w" (K, N), "cost", "w0", "price0", "err" (K,), "status" (K,)
+        int8, "counts" (4,) int64 indexed by LOMPC_QP_* (ok, repaired, failed, invalid), "ws" when given.
+        ``out`` reuses the buffers of an earlier result.  The loaded parameter sets (``set_params``) stay
+        as they are.  ``check`` synchronises once and raises the reference's types in its order, as
+        ``solve_batch`` does: AssertionError if any gamma > y_max, else ValueError for negative or NaN
+        parameters (host arrays are tested before the launch, device tensors from the kernel's tally and
+        a re-test of gamma on the device), SolverError for QPs without a certified optimum.
+        """
+        torch = _torch()
+        N, dev = self.N, f"cuda:{self.device}"
+        host = [x for x in (lmbd, lmbd_r, gamma) if not isinstance(x, torch.Tensor)]
+        if check and host:  # lompc.py:87, then cvxpy's nonneg Parameters (lompc.py:78-82)
+            if not isinstance(gamma, torch.Tensor) and np.any(np.asarray(gamma, dtype=np.float64) > self.y_max):
+                raise AssertionError("gamma <= y_max required")
+            if any(not np.all(np.asarray(x, dtype=np.float64) >= 0) for x in host):
+                raise ValueError("Parameter value must be nonnegative.")
+        g = self._dev(gamma).reshape(-1)
+        K = g.numel()
+        lm = self._dev(lmbd)
+        if lm.dim() == 1:
+            if lm.shape[0] != 3 * N:
+                raise ValueError(f"lmbd must have 3N = {3 * N} entries")
+            stride = 0
+        else:
+            if lm.dim() != 2 or tuple(lm.shape) != (K, 3 * N):
+                raise ValueError(f"lmbd must be (K, 3N) = ({K}, {3 * N}) or (3N,)")
+            stride = 3 * N
+        lr = self._dev(lmbd_r).reshape(-1)
+        if lr.numel() == 1 and K != 1:
+            lr = lr.expand(K).contiguous()
+        if lr.numel() != K:
+            raise ValueError("lmbd_r must be a scalar or have one entry per QP")
+        wr = None if w_ref is None else self._dev(w_ref).reshape(K, N)
+        if warm and ws is None:
+            raise ValueError("solve_many: warm=True needs the working sets ws of an earlier call")
+        if ws is not None and not (isinstance(ws, torch.Tensor) and ws.dtype == torch.uint8 and ws.is_cuda
+                                   and ws.device.index == self.device and tuple(ws.shape) == (K, 64)
+                                   and ws.is_contiguous()):
+            raise ValueError(f"ws must be a contiguous uint8 tensor ({K}, 64) on {dev}")
+        res = {} if out is None else out
+
+        def buf(name, shape, dtype=torch.float64, want=True):
+            if not want:
+                return None
+            t = res.get(name)
+            if t is None or tuple(t.shape) != tuple(shape) or t.dtype != dtype:
+                t = torch.empty(shape, dtype=dtype, device=dev)
+                res[name] = t
+            return t
+
+        w = buf("w", (K, N), want=want_w)
+        cost = buf("cost", (K,), want=want_cost)
+        w0 = buf("w0", (K,), want=want_w0)
+        price0 = buf("price0", (K,), want=want_price0)
+        err = buf("err", (K,), want=wr is not None)
+        status = buf("status", (K,), torch.int8, want=want_status)
+        counts = buf("counts", (4,), torch.int64)
+        if K == 0:  # (empty tensors have no address to pass as lmbd and gamma)
+            counts.zero_()
+        else:
+            rc = self._lib.lompc_solve_many(self._ctx, K, _ptr(lm), stride, _ptr(lr), _ptr(g), _ptr(wr), _ptr(ws),
+                                            _lib.LOMPC_MANY_WARM if warm else 0, _ptr(w), _ptr(cost), _ptr(w0),
+                                            _ptr(price0), _ptr(err), _ptr(status), _ptr(counts), self._stream())
+            self._check_rc(rc)
+        if ws is not None:
+            res["ws"] = ws
+        res["_keep"] = (lm, lr, g, wr)  # (alive until the caller's stream has used them)
+        if check:
+            n = counts.cpu().numpy()  # the one synchronisation
+            if n[_lib.LOMPC_QP_INVALID]:
+                if bool((g > self.y_max).any()):
+                    raise AssertionError("gamma <= y_max required")
+                raise ValueError("Parameter value must be nonnegative.")
+            if n[_lib.LOMPC_QP_FAILED]:
+                raise SolverError(f"{int(n[_lib.LOMPC_QP_FAILED])} QPs without a certified optimum")
+        return res
 
     def profile(self, enable: bool | None = None, read: bool = False, reset: bool = False):
         """Kernel-time profiling of the per-EV evaluation kernel (HIP events)."""

@@ -142,6 +142,50 @@ int lompc_run(lompc_ctx* ctx, int64_t S, const double* lmbd, const double* lmbd_
 int lompc_solve_host(lompc_ctx* ctx, const double* lmbd, double lmbd_r,
                      double gamma, double* w, double* cost);
 
+/* K unrelated QPs, each with its own prices (lmbd_k, lmbd_r_k, gamma_k), in ONE launch: one wave per
+ * QP, solved from a cold working set and KKT-certified like every other solve of the engine.
+ * Replaces a loop of LoMPC.solve_lompc (lompc.py:137-156) over QPs that share no price vector — the
+ * call shape of the reference's own harness (test/test_lompc.py:30-40 draws lmbd, lmbd_r and gamma
+ * anew for each solve) and of per-EV (personalised) incentives.
+ * Every pointer is a device pointer owned by the caller; 8-byte alignment suffices for the doubles and
+ * int64, the bytes need none.  Asynchronous on ``stream``; the call allocates, copies and synchronises
+ * nothing (what a stream capture requires; the tests do not exercise a capture).  It is stateless with respect to the context: it reads
+ * neither the sets of lompc_set_params nor the mode, and leaves lompc_last_status, the status rows
+ * and the context's transient plan untouched.
+ *   K           QPs; 0 is accepted (nothing launched, counts zeroed if given)
+ *   lmbd        dev  [K] vectors of 3N unit prices >= 0, vector k at lmbd + k lmbd_stride
+ *   lmbd_stride doubles between price vectors: 0 = one vector shared by all QPs, else >= 3N (the
+ *               padding between vectors is never read)
+ *   lmbd_r      dev  [K]      robustness price >= 0 of each QP, or NULL (= 0 for all)
+ *   gamma       dev  [K]      gamma_k in [0, y_max]
+ *   w_ref       dev  [K, N]   reference w of each QP's A_bar error, or NULL
+ *   ws          dev  [K, 64]  uint8 working sets (one byte per stage, states 0 .. 2m), or NULL: when
+ *                             given, always WRITTEN with each QP's final working set (bytes of stages
+ *                             >= N: 0); with LOMPC_MANY_WARM also READ as the start of each solve
+ *   flags       0 or LOMPC_MANY_WARM: start the fp64 active-set iteration of QP k from ws[k] (bytes
+ *               above 2m are clamped to 2m, stages >= N ignored; no fp32 working-set search first) —
+ *               for callers who iterate prices per EV; any working set gives the same certified optimum
+ *   w           dev  [K, N]   optimal w_k (row-major), or NULL
+ *   cost        dev  [K]      optimal cost incl. constant (lompc.py:155), or NULL
+ *   w0          dev  [K]      w_k[0], the same bits as w[k, 0], or NULL
+ *   price0      dev  [K]      LoMPC.get_price0(w_k, lmbd_k, lmbd_r_k) (lompc.py:164-170), or NULL
+ *   err         dev  [K]      ||w_k - w_ref_k||_{A_bar}, A_bar = A'A + (lmbd_r_k / delta) I
+ *                             (price_solver.py:191-192, :207), or NULL; needs w_ref
+ *   status      dev  [K]      int8 LOMPC_QP_* per QP, or NULL: OK (certified), REPAIRED (certified after
+ *                             the primal active set), FAILED (no certificate; the row and scalars hold
+ *                             the last iterate), INVALID (gamma outside [0, y_max], a negative price, or
+ *                             NaN in any of them: the row and every requested scalar are NaN)
+ *   counts      dev  [4]      int64 tallies indexed by LOMPC_QP_* (ok, repaired, failed, invalid), or NULL
+ * A QP's outputs depend on its own inputs only: not on K, on its position, or on its neighbours.
+ * LOMPC_ERR_INVALID_ARG with nothing written: K < 0; NULL ctx, lmbd or gamma; 0 < lmbd_stride < 3N;
+ * unknown flag bits; LOMPC_MANY_WARM with ws NULL; err without w_ref. */
+#define LOMPC_MANY_WARM 1
+int lompc_solve_many(lompc_ctx* ctx, int64_t K, const double* lmbd, int64_t lmbd_stride,
+                     const double* lmbd_r, const double* gamma, const double* w_ref,
+                     uint8_t* ws, int flags, double* w, double* cost, double* w0,
+                     double* price0, double* err, int8_t* status, int64_t* counts,
+                     void* stream);
+
 /* Synchronise ``stream`` and report the device-side counters of the last
  * lompc_solve_batch: EVs repaired, failed, invalid (any may be NULL). */
 int lompc_last_status(lompc_ctx* ctx, void* stream, int64_t* n_repaired,

@@ -57,6 +57,12 @@ LOMPC_QP_REPAIRED = 1
 LOMPC_QP_FAILED = 2
 LOMPC_QP_INVALID = 3
 
+# lompc_price_step_many's per-QP states
+LOMPC_STEP_RUNNING = 0
+LOMPC_STEP_CONVERGED = 1
+LOMPC_STEP_FAILED = 2
+LOMPC_STEP_INVALID = 3
+
 LOMPC_STAT_COUNT = 0
 LOMPC_STAT_SUM_W0 = 1
 LOMPC_STAT_SUM_PRICE0 = 2
@@ -82,6 +88,7 @@ SIGNATURES = [
     ("lompc_run", _I, [_P, _L, _P, _P, _P, _P, _L, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     ("lompc_solve_host", _I, [_P, _P, _D, _D, _P, _P]),
     ("lompc_solve_many", _I, [_P, _L, _P, _L, _P, _P, _P, _P, _I, _P, _P, _P, _P, _P, _P, _P, _P]),
+    ("lompc_price_step_many", _I, [_P, _L, _I, _D, _P, _P, _P, _L, _P, _P, _D, _P, _L, _P, _P, _P, _P, _P]),
     ("lompc_last_status", _I, [_P, _P, _P, _P, _P]),
     ("lompc_profile_enable", _I, [_P, _I]),
     ("lompc_profile_read", _I, [_P, _P, _P, _I]),

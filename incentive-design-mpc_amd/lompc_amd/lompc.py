@@ -11,7 +11,8 @@ optimal cost including its constant, exactly what ``self.w.value`` /
 
 Added for the batched hot path: ``set_params`` (S parameter sets at once) and
 ``solve_batch`` (B QPs in one device call with fused per-set reductions), and
-``solve_many`` (K QPs that each have their own prices, in one launch).
+``solve_many`` (K QPs that each have their own prices, in one launch) with
+``price_step_many`` (the price-gradient step of K such QPs in one launch).
 
 All numerics run in the HIP extension (``liblompc_amd.so``); this module only
 moves buffers and maps status codes to the reference's exception types:
@@ -27,7 +28,7 @@ from dataclasses import dataclass
 import numpy as np
 
 from . import _lib
-from .settings import MAX_BAT_CHARGE_RATE, MAX_MAX_BAT_SOC, MIN_MAX_BAT_SOC, LOMPC_MODE
+from .settings import MAX_BAT_CHARGE_RATE, MAX_MAX_BAT_SOC, MIN_MAX_BAT_SOC, LOMPC_MODE, PRICE_SOLVER_EPS_REG
 
 
 class SolverError(Exception):
@@ -393,6 +394,96 @@ class LoMPC:
                 raise ValueError("Parameter value must be nonnegative.")
             if n[_lib.LOMPC_QP_FAILED]:
                 raise SolverError(f"{int(n[_lib.LOMPC_QP_FAILED])} QPs without a certified optimum")
+        return res
+
+    def price_step_many(self, w, w_ref, lmbd, lmbd_r, *, price_type: str, err=None, tol: float = 0.0, state=None,
+                        iters=None, eps_reg: float = PRICE_SOLVER_EPS_REG, out: dict | None = None,
+                        in_place: bool = False) -> dict:
+        """The price-gradient step (price_solver.py:216-246) of K unrelated QPs in one launch
+        (lompc_price_step_many), each at its own (w, w_ref, lmbd, lmbd_r): what a loop of
+        ``PriceSolver._price_gradient_descent_step`` over one-EV solvers returns, without the loop, the copy of
+        ``w`` to the host and the copy of the prices back.
+
+        w, w_ref: (K, N) — ``solve_many``'s "w" and its ``w_ref``; lmbd: (K, 3N) (rows >= r are not read) or
+        (K, r); lmbd_r: (K,), a scalar or None (= 0); array-likes or device tensors.  price_type: "linear"
+        (r = 2N) or "linear-convex" (r = 3N).  err: (K,) — ``solve_many``'s "err": a QP with err <= tol is marked
+        converged instead of stepped (price_solver.py:125); None: every running QP steps.  state: int8 device
+        tensor (K,) of LOMPC_STEP_*, read and written in place (QPs that are not RUNNING keep their prices);
+        iters: int32 device tensor (K,), +1 per step taken; both optional.
+        Returns a dict of device tensors: "lmbd" (K, 3N), the next prices (rows >= r zero; NaN rows for QPs
+        with NaN or negative inputs, the unchanged prices for converged, failed and frozen ones), "dec" (K,)
+        the predicted dual cost decrease, "counts" (4,) int64 by LOMPC_STEP_* (running, converged, failed,
+        invalid), and "state" / "iters" when given.  ``out`` reuses the buffers of an earlier result.
+        ``in_place``: lmbd must be a contiguous fp64 device tensor (K, 3N); it is overwritten and returned as
+        "lmbd".  Nothing is synchronised and nothing raises for a single QP: read "counts" or "state".
+        """
+        torch = _torch()
+        if price_type not in ("linear", "linear-convex"):
+            raise ValueError('price_type must be "linear" or "linear-convex"')
+        N, dev = self.N, f"cuda:{self.device}"
+        r = 2 * N if price_type == "linear" else 3 * N
+        wk = self._dev(w)
+        if wk.dim() != 2 or wk.shape[1] != N:
+            raise ValueError(f"w must be (K, N) = (K, {N})")
+        K = wk.shape[0]
+        wr = self._dev(w_ref)
+        if tuple(wr.shape) != (K, N):
+            raise ValueError(f"w_ref must be (K, N) = ({K}, {N})")
+        if in_place:
+            if not (isinstance(lmbd, torch.Tensor) and lmbd.dtype == torch.float64 and lmbd.is_cuda
+                    and lmbd.device.index == self.device and tuple(lmbd.shape) == (K, 3 * N) and lmbd.is_contiguous()):
+                raise ValueError(f"in_place: lmbd must be a contiguous float64 tensor ({K}, {3 * N}) on {dev}")
+            lm = lmbd
+        else:
+            lm = self._dev(lmbd)
+            if lm.dim() != 2 or lm.shape[0] != K or lm.shape[1] not in (r, 3 * N):
+                raise ValueError(f"lmbd must be (K, 3N) = ({K}, {3 * N}) or (K, r) = ({K}, {r})")
+        lr = None
+        if lmbd_r is not None:
+            lr = self._dev(lmbd_r).reshape(-1)
+            if lr.numel() == 1 and K != 1:
+                lr = lr.expand(K).contiguous()
+            if lr.numel() != K:
+                raise ValueError("lmbd_r must be None, a scalar or have one entry per QP")
+        er = None
+        if err is not None:
+            er = self._dev(err).reshape(-1)
+            if er.numel() != K:
+                raise ValueError("err must have one entry per QP")
+        for name, t, dt in (("state", state, torch.int8), ("iters", iters, torch.int32)):
+            if t is not None and not (isinstance(t, torch.Tensor) and t.dtype == dt and t.is_cuda
+                                      and t.device.index == self.device and tuple(t.shape) == (K,) and t.is_contiguous()):
+                raise ValueError(f"{name} must be a contiguous {dt} tensor ({K},) on {dev}")
+        res = {} if out is None else out
+
+        def buf(name, shape, dtype=torch.float64):
+            t = res.get(name)
+            if t is None or tuple(t.shape) != tuple(shape) or t.dtype != dtype or t.device.index != self.device \
+                    or not t.is_contiguous():
+                t = torch.empty(shape, dtype=dtype, device=dev)
+                res[name] = t
+            return t
+
+        if in_place:
+            nxt = res["lmbd"] = lm
+        else:
+            if res.get("lmbd") is lm:  # (an earlier result's buffer passed back as the input: not in place)
+                del res["lmbd"]
+            nxt = buf("lmbd", (K, 3 * N))
+        dec = buf("dec", (K,))
+        counts = buf("counts", (4,), torch.int64)
+        if K == 0:  # (empty tensors have no address to pass)
+            counts.zero_()
+        else:
+            rc = self._lib.lompc_price_step_many(self._ctx, K, r, float(eps_reg), _ptr(wk), _ptr(wr), _ptr(lm),
+                                                 lm.shape[1], _ptr(lr), _ptr(er), float(tol), _ptr(nxt), 3 * N,
+                                                 _ptr(dec), _ptr(state), _ptr(iters), _ptr(counts), self._stream())
+            self._check_rc(rc)
+        if state is not None:
+            res["state"] = state
+        if iters is not None:
+            res["iters"] = iters
+        res["_keep"] = (wk, wr, lm, lr, er)  # (alive until the caller's stream has used them)
         return res
 
     def profile(self, enable: bool | None = None, read: bool = False, reset: bool = False):

@@ -38,7 +38,7 @@ from . import _lib
 from . import settings as _settings
 from .lompc import BatchPlan, LoMPC, LoMPCConstants, SolverError
 from .price_regularizer import PriceRegularizer, PriceRegularizerError
-from .settings import PRICE_SOLVER_EPS_REG, PRICE_SOLVER_EPS_TOL
+from .settings import MAX_PRICE_SOLVER_ITERATIONS, PRICE_SOLVER_EPS_REG, PRICE_SOLVER_EPS_TOL
 
 
 def _torch():
@@ -759,6 +759,72 @@ class PriceSolver:
         for k in range(K):
             self._check_stats(st[k])
         return out["w0"], st[:, 0, _lib.LOMPC_STAT_SUM_PRICE0].copy()
+
+
+def personal_prices(lompc: LoMPC, price_type: str, gamma, w_ref, lmbd_r, *, lmbd0=None,
+                    max_iter: int = MAX_PRICE_SOLVER_ITERATIONS, eps_tol: float = PRICE_SOLVER_EPS_TOL,
+                    eps_reg: float = PRICE_SOLVER_EPS_REG) -> dict:
+    """Per-EV (personalised) prices: K one-EV instances of ``compute_optimal_prices``' loop
+    (price_solver.py:102-140) side by side, without the final regularisation — EV k, with gamma[k] left to
+    charge, is priced towards its own w_ref[k] under its own lmbd_r[k].
+
+    For a one-EV population y0_rng = 0 and gamma_sc = gamma, so the tolerance is ``eps_tol``
+    (price_solver.py:182-186), the central QP is the EV's own and both of the reference's error kinds are
+    ``solve_many``'s "err".  The loop is driven from the host with two launches per iteration and nothing but
+    a 32-byte tally read back: ``price_step_many`` in place (the convergence test fused in front of the
+    step), then — while any EV is still running — ``solve_many(warm=True)`` from the kept working sets.  EVs
+    that have finished are re-solved at their unchanged prices (the same optimum, from its own working set); they
+    are not compacted away.
+
+    gamma: (K,); w_ref: (K, N); lmbd_r: (K,) or a scalar; lmbd0: start prices (K, r) or (K, 3N) (rows >= r
+    are ignored), zeros by default; array-likes or device tensors.
+    Returns device tensors "lmbd" (K, 3N) (rows >= r zero), "w" (K, N) the optimum at the returned prices,
+    "err" (K,) its error, "state" (K,) int8 LOMPC_STEP_* (RUNNING: the EV reached ``max_iter`` steps; FAILED /
+    INVALID: its price QP had no certified optimum / its inputs were NaN — its prices are the last good ones,
+    or NaN), "iters" (K,) int32 the steps taken, and "solves", the number of ``solve_many`` calls made
+    (max(iters) + 1).  The reference's ``solver_stats["iter"]`` is ``iters`` for a converged EV and
+    ``max_iter - 1`` for one that reached the cap.  The dual-cost-decrease history is not kept.
+    Raises as ``solve_many(check=True)`` does on the first solve; SolverError if a later LoMPC solve was left
+    without a certified optimum.
+    """
+    torch = _torch()
+    if price_type not in ("linear", "linear-convex"):
+        raise ValueError('price_type must be "linear" or "linear-convex"')
+    N = lompc.N
+    r = 2 * N if price_type == "linear" else 3 * N
+    dev = f"cuda:{lompc.device}"
+    g = lompc._dev(gamma).reshape(-1)
+    K = g.numel()
+    wr = lompc._dev(w_ref).reshape(K, N)
+    lr = lompc._dev(lmbd_r).reshape(-1)
+    if lr.numel() == 1 and K != 1:
+        lr = lr.expand(K).contiguous()
+    if lr.numel() != K:
+        raise ValueError("lmbd_r must be a scalar or have one entry per EV")
+    lm = torch.zeros((K, 3 * N), dtype=torch.float64, device=dev)
+    if lmbd0 is not None:
+        l0 = lompc._dev(lmbd0)
+        if l0.dim() != 2 or l0.shape[0] != K or l0.shape[1] not in (r, 3 * N):
+            raise ValueError(f"lmbd0 must be (K, r) = ({K}, {r}) or (K, 3N) = ({K}, {3 * N})")
+        lm[:, :r] = l0[:, :r]
+    ws = torch.zeros((K, 64), dtype=torch.uint8, device=dev)
+    state = torch.zeros(K, dtype=torch.int8, device=dev)
+    iters = torch.zeros(K, dtype=torch.int32, device=dev)
+    sol = lompc.solve_many(lm, lr, g, w_ref=wr, ws=ws, want_cost=False)  # (checked: the inputs' validity)
+    solves = 1
+    unsolved = torch.zeros((), dtype=torch.int64, device=dev)
+    step = {}
+    for _ in range(int(max_iter)):
+        lompc.price_step_many(sol["w"], wr, lm, lr, price_type=price_type, err=sol["err"], tol=eps_tol, state=state,
+                              iters=iters, eps_reg=eps_reg, out=step, in_place=True)
+        if K == 0 or int(step["counts"].cpu()[_lib.LOMPC_STEP_RUNNING]) == 0:  # the iteration's one read
+            break
+        lompc.solve_many(lm, lr, g, w_ref=wr, ws=ws, warm=True, want_cost=False, out=sol, check=False)
+        unsolved += sol["counts"][_lib.LOMPC_QP_FAILED]
+        solves += 1
+    if int(unsolved):
+        raise SolverError(f"{int(unsolved)} LoMPC solves of the loops without a certified optimum")
+    return {"lmbd": lm, "w": sol["w"], "err": sol["err"], "state": state, "iters": iters, "solves": solves}
 
 
 def compute_optimal_prices_parallel(jobs, lmbd_r: float, max_parts_per_launch: int = 0):

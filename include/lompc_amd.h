@@ -186,6 +186,59 @@ int lompc_solve_many(lompc_ctx* ctx, int64_t K, const double* lmbd, int64_t lmbd
                      double* price0, double* err, int8_t* status, int64_t* counts,
                      void* stream);
 
+/* The price-gradient step (PriceSolver._price_gradient_descent_step, price_solver.py:216-246: what
+ * lompc_price_step does for one QP on the host) for K unrelated QPs in ONE launch, each with its own w,
+ * w_ref, prices and lmbd_r, with the price loop's convergence test (price_solver.py:125) in front of it:
+ * the other half of a per-EV (personalised) price iteration beside lompc_solve_many, whose w and err it
+ * reads where they lie.  One wave per QP; the method is the device price loop's (primal-dual active set
+ * from lmbd's free set, primal active set from x = 0 as the fallback, KKT-certified at 1e-11 (1 + max |q|)).
+ * Every pointer is a device pointer owned by the caller; 8-byte alignment suffices for the doubles and
+ * int64, 4-byte for iters.  Asynchronous on ``stream``; the call allocates, copies and synchronises nothing.
+ * Of the context it reads the constants only (N, delta, theta, w_max, the device; m = 2 delta theta^2): no
+ * parameter set, no mode, and nothing is kept between calls (the factor of A_bar is computed per QP).
+ *   K            QPs; 0 is accepted (nothing launched, counts zeroed if given)
+ *   r            price rows: 2N (linear) or 3N (linear-convex)
+ *   eps_reg      > 0, the regularisation of the step's QP (settings.py PRICE_SOLVER_EPS_REG)
+ *   w            dev  [K, N]   each QP's LoMPC optimum at lmbd (lompc_solve_many's w)
+ *   w_ref        dev  [K, N]   each QP's reference
+ *   lmbd         dev  [K] vectors of r unit prices >= 0, vector k at lmbd + k lmbd_stride; rows >= r and
+ *                              the padding between vectors are never read
+ *   lmbd_stride  doubles between the vectors read, >= r
+ *   lmbd_r       dev  [K]      robustness price >= 0 of each QP (kappa_k = lmbd_r_k / delta), or NULL (= 0)
+ *   err          dev  [K]      each QP's error for the convergence test (lompc_solve_many's err), or NULL:
+ *                              no test
+ *   tol          a QP with err_k <= tol has converged
+ *   lmbd_next    dev  [K] vectors of 3N doubles, vector k at lmbd_next + k next_stride: rows < r as below,
+ *                              rows r .. 3N-1 always 0; the padding between vectors is never written
+ *   next_stride  doubles between the vectors written, >= 3N
+ *   dec          dev  [K]      the step's predicted dual cost decrease (:236, :244-245), or NULL
+ *   state        dev  [K]      int8 LOMPC_STEP_*, read and written, or NULL (every QP RUNNING, nothing kept)
+ *   iters        dev  [K]      int32 steps taken, read and written (+1 per successful step), or NULL
+ *   counts       dev  [4]      int64 tallies of the QPs' states after the call, indexed by LOMPC_STEP_*, or NULL
+ * Per QP k, in this order:
+ *   1. state given and state_k != RUNNING: frozen.  Rows < r of lmbd_next are lmbd's bits, dec_k = 0,
+ *      state_k and iters_k stay (a value outside LOMPC_STEP_* freezes as well and is tallied as INVALID).
+ *   2. NaN in w_k, w_ref_k, rows < r of lmbd_k, lmbd_r_k or err_k, a negative price or a negative lmbd_r_k:
+ *      state_k = INVALID, rows < r of lmbd_next and dec_k NaN.
+ *   3. err given and err_k <= tol: state_k = CONVERGED, the prices copied as in 1., dec_k = 0.
+ *   4. the step.  Certified: rows < r of lmbd_next = argmin, dec_k its decrease, iters_k += 1, state_k stays
+ *      RUNNING.  Not certified: state_k = FAILED, the prices copied as in 1., dec_k = NaN.
+ * A QP's outputs depend on its own inputs only: not on K, on its position, on the strides or on its
+ * neighbours.  lmbd_next may be lmbd itself with next_stride == lmbd_stride (in place: every wave reads its
+ * row before it writes); otherwise the two ranges must not overlap at all.
+ * LOMPC_ERR_INVALID_ARG with nothing written: NULL ctx, w, w_ref, lmbd or lmbd_next; K < 0; r not 2N or 3N;
+ * eps_reg <= 0 (or NaN); lmbd_stride < r; next_stride < 3N; lmbd_next overlapping lmbd other than exactly
+ * in place. */
+#define LOMPC_STEP_RUNNING 0
+#define LOMPC_STEP_CONVERGED 1
+#define LOMPC_STEP_FAILED 2
+#define LOMPC_STEP_INVALID 3
+int lompc_price_step_many(lompc_ctx* ctx, int64_t K, int r, double eps_reg, const double* w,
+                          const double* w_ref, const double* lmbd, int64_t lmbd_stride,
+                          const double* lmbd_r, const double* err, double tol, double* lmbd_next,
+                          int64_t next_stride, double* dec, int8_t* state, int32_t* iters,
+                          int64_t* counts, void* stream);
+
 /* Synchronise ``stream`` and report the device-side counters of the last
  * lompc_solve_batch: EVs repaired, failed, invalid (any may be NULL). */
 int lompc_last_status(lompc_ctx* ctx, void* stream, int64_t* n_repaired,
